@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: Mcells/s of FlwdirRaster.upstream_area("cell") on the synthetic
 90000 x 90000 D8 raster of BASELINE.json configs[3] (8.1 Gcells; it fits one 288 GB MI355X), with the
-HBM-roofline fraction of the dominant kernel and of the whole pass, the graph statistics SURVEY.md §8d
-asks for, and the single-thread CPU baseline (the oracle restatement of the reference's serial
-algorithm) timed on the same host on a bounded sample of the same raster.
+HBM-roofline fraction of the dominant kernel and of the whole pass.  With --full the line also carries
+the graph statistics SURVEY.md §8d asks for, the full-size invariants and the single-thread CPU baseline
+(the oracle restatement of the reference's serial algorithm) timed on the same host on a bounded sample
+of the same raster.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--regime river|rough|meander]
-                    [--no-cpu-baseline] [--no-secondary]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-secondary]]
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.  --dump-outputs DIR
+then writes what the last timed step computed to DIR/*.npy (float64; a fixed sample of rows when the
+whole result would exceed 48 MiB, see dump_outputs).  --full adds everything that takes work or runs of its
+own: the statistics and invariant passes, the CPU baseline, the secondary lines below and the record of
+the N = 1 run that the N > 1 lines compare against.
 
 A "step" is one complete pass of the hot path over the raster: device-resident uint8 D8 codes in ->
 device-resident int32 upstream cell counts out, INCLUDING the decode / pit rule / validation of the
@@ -21,8 +28,8 @@ index); under a launcher (`python -m torch.distributed.run --nproc-per-node N ..
 launcher's RANK / WORLD_SIZE / MASTER_* are used.  Either way the host side (barrier, max-reduce of the wall
 time, rendezvous of the RCCL unique id) is the library's torch-free TCP group; no PyTorch is imported.
 
-With N = 1 the JSON line also carries `secondary`: the 10000 x 10000 pass (configs[1]) and the
-configs[2] operations (float32 accuflux + Strahler order at 30000 x 30000), each with its own
+With N = 1 and --full the JSON line also carries `secondary`: the 10000 x 10000 pass (configs[1]) and
+the configs[2] operations (float32 accuflux + Strahler order at 30000 x 30000), each with its own
 roofline object.
 """
 from __future__ import annotations
@@ -114,8 +121,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=90000, help="the raster is size x size (split over the GPUs)")
     ap.add_argument("--regime", default="river", choices=sorted(REGIMES))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the statistics / invariant passes, the CPU baseline and the secondary lines (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (single-GPU upstream_area line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary lines")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the raster given to the CPU baseline (0=auto)")
     ap.add_argument("--op", choices=["upstream_area", "hand", "basins", "accuflux", "strahler"], default="upstream_area",
                     help="hand / basins: BASELINE configs[4] — the sharded collective on the 36000 x 72000 tile (rows x cols; "
@@ -131,7 +142,12 @@ def parse():
                          "for RCCL (tests/rccl_loopback) so that the world > 1 RCCL branches of the library run with ranks "
                          "sharing a GPU; the line names the binding (config.rccl_binding = 'loopback stand-in'); no timing "
                          "claim can rest on it")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.gpus != 1 or a.op != "upstream_area" or a.ops):
+        ap.error("--dump-outputs: only the single-GPU upstream_area line (--gpus 1, no --op / --ops)")
+    return a
 
 
 LOOPBACK_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tests", "rccl_loopback", "librccl_loopback.so")
@@ -269,8 +285,38 @@ def filled_mosaic(min_edge=10000, base=2048, device=0):
     return np.ascontiguousarray(np.tile(framed, reps))
 
 
-def upa_line(nrow, ncol, regime, steps, warmup, device, cpu=True, cpu_rows=0, checks=True, invariant_checks=None):
-    """The upstream_area("cell") pass on one GPU: returns the JSON fields of one bench line."""
+DUMP_BYTES = 48 << 20  # dumped rows at most; + 8 B per raster row of row sums: under 64 MB up to --size 10^6
+
+
+def dump_outputs(out_buf, nrow, ncol, path, seed=20240):
+    """--dump-outputs: the int32 upstream cell counts the last timed step left in `out_buf` (what a caller of the pass
+    receives), as float64 (exact for int32) in PATH/upstream_area_cell_rows.npy, one row per dumped raster row, and the
+    indices of those rows in PATH/upstream_area_cell_row_index.npy.  Every row when the raster fits DUMP_BYTES, else a
+    fixed sample: the first row, the last (where the river regime's pits gather whole basins) and rows drawn with a
+    fixed seed, so that two builds run with the same arguments dump the same cells.  Every cell counts in
+    PATH/upstream_area_cell_row_sums.npy: the sum of each row (int64 on the device, exact in float64 below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    cols = min(ncol, DUMP_BYTES // 8)
+    k = max(1, min(nrow, DUMP_BYTES // (8 * cols)))
+    if k >= nrow:
+        rows = np.arange(nrow)
+        whole = out_buf.download(np.int32, (nrow, ncol))
+        vals, sums = whole[:, :cols], whole.sum(axis=1, dtype=np.int64)
+    else:
+        rng = np.random.default_rng(seed)
+        drawn = rng.choice(np.arange(1, nrow - 1), size=max(0, k - 2), replace=False) if nrow > 2 else []
+        rows = np.unique(np.concatenate([[0, nrow - 1], drawn]).astype(np.int64))[:k]
+        vals = np.stack([out_buf.download(np.int32, (ncol,), offset_bytes=int(r) * ncol * 4)[:cols] for r in rows])
+        sums = np.array([_hip.checksum_i32(_hip.ptr(out_buf).value + r * ncol * 4, ncol, out_buf.device) for r in range(nrow)],
+                        np.int64)
+    np.save(os.path.join(path, "upstream_area_cell_rows.npy"), vals.astype(np.float64))
+    np.save(os.path.join(path, "upstream_area_cell_row_index.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "upstream_area_cell_row_sums.npy"), sums.astype(np.float64))
+
+
+def upa_line(nrow, ncol, regime, steps, warmup, device, cpu=True, cpu_rows=0, checks=True, invariant_checks=None, dump_dir=None):
+    """The upstream_area("cell") pass on one GPU: returns the JSON fields of one bench line.  `dump_dir`: the result of
+    the last timed step goes there (dump_outputs) before any check runs."""
     if regime == "rhine_mosaic_device":
         # the reference's Rhine raster (tests/golden/rhine.npz) tiled on the DEVICE: the base raster (0.7 MB) is uploaded,
         # pfd_synth_mosaic writes the nrow x ncol mosaic (one-cell nodata frame per copy) straight into HBM
@@ -301,6 +347,8 @@ def upa_line(nrow, ncol, regime, steps, warmup, device, cpu=True, cpu_rows=0, ch
     total, per, timed = timed_steps(lambda prof: one_step(d8_buf, out_buf, nrow, ncol, device, profile=prof), steps,
                                     warmup, device, after_warmup=lambda: alloc0.update(_hip.alloc_stats()))
     alloc1 = _hip.alloc_stats()
+    if dump_dir:
+        dump_outputs(out_buf, nrow, ncol, dump_dir)
     ms_per_step = total / steps * 1e3
     segs, info = mean_segments([t[0] for t in timed]), timed[-1][1]
     out = dict(value=round(n * steps / total / 1e6, 2), ms_per_step=round(ms_per_step, 3),
@@ -607,7 +655,7 @@ def km2_line(nrow, ncol, synth, label, steps, device):
     return lines
 
 
-N1_RECORD = os.path.join(ROOT, ".bench_n1.json")  # (git-ignored scratch: lets the N > 1 lines quote their speed-up)
+N1_RECORD = os.path.join(ROOT, ".bench_n1.json")  # (git-ignored scratch of --full: lets the N > 1 lines quote their speed-up)
 
 
 def api_lines(nrow, ncol, synth, device, reps=3):
@@ -790,7 +838,7 @@ def run_distributed(a, rank, world, local):
                    invariants=dict(result_checksum=csum,
                                    last_row_pit_sum_equals_n_valid=bool(pit_sum == n_valid) if a.regime == "river" else None))
         n1 = load_n1_record(a)
-        if n1 is not None:  # the N = 1 run of the same raster on this box (bench.py writes it at N = 1)
+        if n1 is not None:  # the N = 1 run of the same raster on this box (bench.py --full writes it at N = 1)
             out["speedup_vs_n1"] = round(n1["ms_per_step"] / ms_per_step, 3)
             out["n1_ms_per_step"] = n1["ms_per_step"]
             if n1.get("result_checksum") is not None:
@@ -1005,6 +1053,22 @@ def rank_environments(n, n_devices, port, base_env=None, loopback=False):
     return envs
 
 
+def visible_devices(timeout=300.0):
+    """The number of HIP devices, counted by a short-lived child process: the parent of self-spawned ranks only waits
+    for them, and with no GPU context of its own it is not one more process that has the GPU open while they run."""
+    import subprocess
+
+    code = "import sys; sys.path.insert(0, sys.argv[1]); from pyflwdir_amd import _hip; print(_hip.device_count())"
+    try:
+        r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired:
+        raise SystemExit(f"bench.py: counting the HIP devices did not finish in {timeout:g} s") from None
+    try:
+        return int(r.stdout.split()[-1])
+    except (IndexError, ValueError):
+        raise SystemExit(f"bench.py: could not count the HIP devices: {r.stderr.strip()[-600:]}") from None
+
+
 def spawn_ranks(a, argv=None, n_devices=None, timeout=3000.0, script=None, extra_env=None, out=None):
     """`python bench.py --gpus N` without a launcher: start the N ranks as plain processes (one per GPU), pass rank
     0's JSON line through on stdout (or write it to the file object ``out``), return the first non-zero exit code.
@@ -1012,7 +1076,7 @@ def spawn_ranks(a, argv=None, n_devices=None, timeout=3000.0, script=None, extra
     collective."""
     import subprocess
 
-    n_devices = _hip.device_count() if n_devices is None else n_devices
+    n_devices = visible_devices() if n_devices is None else n_devices
     if n_devices < 1:
         raise SystemExit("bench.py: no HIP device visible")
     argv = sys.argv[1:] if argv is None else argv
@@ -1091,6 +1155,8 @@ def main():
     if a.op != "upstream_area":  # configs[4]: the sharded collectives (also with one rank: the N = 1 reference line)
         return run_distributed_op(a, rank, world, local)
     if world > 1 or os.environ.get("PFD_BENCH_FORCE_DIST"):  # the env knob runs the RCCL path with 1 rank
+        if a.dump_outputs:
+            raise SystemExit("bench.py --dump-outputs: only the single-GPU upstream_area line")
         return run_distributed(a, rank, world, local)
     device = local
     reserve_working_memory(device, rank_reserve_gib(64.0, 1))
@@ -1103,14 +1169,16 @@ def main():
                              ops=("hand", "basins"))
         print(json.dumps(dict(ops=lines)))
         return
-    line, cfg = upa_line(a.size, a.size, a.regime, a.steps, a.warmup, device, cpu=not a.no_cpu_baseline,
-                         cpu_rows=a.cpu_rows)
+    # (a plain run: the timed steps and what they measure themselves; --full: the checks, the CPU baseline, the side lines)
+    line, cfg = upa_line(a.size, a.size, a.regime, a.steps, a.warmup, device, cpu=a.full and not a.no_cpu_baseline,
+                         cpu_rows=a.cpu_rows, checks=a.full, dump_dir=a.dump_outputs)
     out = dict(metric="Mcells/s upstream_area on D8 raster", value=line.pop("value"), unit="Mcells/s", n_gpus=1,
                steps=a.steps, warmup=a.warmup, ms_per_step=line.pop("ms_per_step"), higher_is_better=True,
                scaling="strong", vs_baseline=None, dtype="int32", data="synthetic", config=cfg)
     out.update(line)
-    save_n1_record(a, out)
-    if not a.no_secondary:
+    if a.full:
+        save_n1_record(a, out)
+    if a.full and not a.no_secondary:
         try:
             out["secondary"] = secondary_lines(a, device)
         except Exception as exc:  # noqa: BLE001 - the headline line must get out whatever a side line does

@@ -53,7 +53,7 @@ def test_spawn_ranks_ok(tmp_path, capfd):
         g = HostGroup()
         s = g.allreduce(int(os.environ["LOCAL_RANK"]) + 1, "sum")
         g.barrier()
-        print("line from rank", g.rank, "sum", s, "world", g.world, sys.argv[1:])
+        print(f"line from rank {{g.rank}} sum {{s}} world {{g.world}} {{sys.argv[1:]}}")  # (one string: ranks share stderr, unbuffered too)
         g.close()
         """)
     rc = b.spawn_ranks(types.SimpleNamespace(gpus=3), argv=["--gpus", "3"], n_devices=1, timeout=120, script=script)
@@ -117,3 +117,24 @@ def test_spawn_falls_back_to_the_host_transport(tmp_path, capfd, monkeypatch):
     rc = b.spawn_with_fallback(types.SimpleNamespace(gpus=2), spawn=spawn, first_timeout=60)
     out, _ = capfd.readouterr()
     assert rc == 3 and out.strip() == ""
+
+
+def test_visible_devices_counts_in_a_child(monkeypatch):
+    """The parent of self-spawned ranks counts the devices in a short-lived child (it holds no GPU context while its ranks
+    run); the count is the library's, and a child that hangs or fails ends bench.py with a message, not a traceback."""
+    import pytest
+
+    b = _bench()
+    from pyflwdir_amd import _hip
+
+    assert b.visible_devices() == _hip.device_count()
+
+    def hang(*args, **kwargs):
+        raise subprocess.TimeoutExpired(args[0], kwargs.get("timeout"))
+
+    monkeypatch.setattr(subprocess, "run", hang)
+    with pytest.raises(SystemExit, match="did not finish in 5 s"):
+        b.visible_devices(timeout=5)
+    monkeypatch.setattr(subprocess, "run", lambda *a, **k: subprocess.CompletedProcess(a[0], 1, "", "HipLibraryMissing: x"))
+    with pytest.raises(SystemExit, match="could not count the HIP devices: HipLibraryMissing"):
+        b.visible_devices()

@@ -54,7 +54,7 @@ def test_bench_spawns_its_own_ranks(gpu_lib):
     (here both on the one GPU, so the records travel through the host group), prints one JSON line, exits 0."""
     args = ["--size", "6000", "--steps", "2", "--warmup", "1"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary"] + args,
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary"] + args,
                          capture_output=True, text=True, timeout=600, env=env)
     assert one.returncode == 0, one.stderr[-2000:]
     ref = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][-1])
@@ -81,7 +81,7 @@ def test_bench_spawns_its_own_ranks(gpu_lib):
 @pytest.mark.parametrize("launcher", ["torchrun", "tcp"])
 def test_two_ranks_on_one_gpu(gpu_lib, launcher):
     args = ["--size", "6000", "--steps", "2", "--warmup", "1"]
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary"] + args,
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary"] + args,
                          capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     ref = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][-1])

@@ -13,7 +13,7 @@ cd /tmp
 if [ "$S" = "c3" ] || [ "$S" = "c5" ]; then
   B="python $R/bench.py --ops $S --steps 2"
 else
-  B="python $R/bench.py --size $S --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+  B="python $R/bench.py --full --size $S --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
 fi
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/fetch -o f -- $B > $O/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/write -o w -- $B > $O/write.log 2>&1
