@@ -307,7 +307,7 @@ extern "C" int pfd_reserve(int device, size_t bytes) {
   }
   // (first use of freshly allocated HBM is slower than the second — measured: a row block's phase A takes 6.5 ms on
   //  fresh blocks against 2.9 ms on recycled ones — so the arena is written once here, where nobody is timing)
-  if (e == hipSuccess && !pfd_knob("PFD_RESERVE_NO_TOUCH")) {
+  if (e == hipSuccess) {
     // (a kernel of its own, not hipMemset: profiles of a pass count the runtime's fill kernel among the pass's clears)
     k_arena_touch<<<4096, 256>>>((uint4 *)base, sz / 16);
     (void)hipDeviceSynchronize();
@@ -533,8 +533,7 @@ static void release_stream(int device, hipStream_t s, bool low = false) {
 
 int pfd_aux_stream(pfd_raster *h) {
   if (!h->stream2) {
-    h->stream2_low = !pfd_knob("PFD_AUX_PRIORITY_SAME");
-    PFDCHK(acquire_stream(h->device, &h->stream2, h->stream2_low));
+    PFDCHK(acquire_stream(h->device, &h->stream2, true));
   }
   if (!h->ev_fork) HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   if (!h->ev_join) HIPCHK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
@@ -642,7 +641,7 @@ static void free_handle(pfd_raster *h) {
   pfd_dfree(h->ctrl);
   if (h->stream2) {
     (void)hipStreamSynchronize(h->stream2);
-    release_stream(h->device, h->stream2, h->stream2_low);
+    release_stream(h->device, h->stream2, true);
   }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);

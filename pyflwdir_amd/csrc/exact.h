@@ -54,9 +54,9 @@ struct ExactPlan {
   uint16_t *toff = nullptr;  // [ntiles * XOFF] start of step s in tord; entries past the last step = total
   u32 *cslot = nullptr;   // [n] slot of a trunk cell (its real slot; post slots follow it); undefined elsewhere
   // The trunk cells of every 64 x 64 tile as a dense list (round 5): {slot, local index | post slots << 12}.  The passes
-  // that visit the trunk cells in raster order (k_xtrunk_demit, k_xtrunk_unscatter) read 8 contiguous bytes per trunk
-  // cell instead of the marks of every cell plus 4 scattered bytes of cslot per trunk cell — a quarter of the cells, one
-  // or two per 64-byte sector along a river.
+  // that visit the trunk cells tile by tile (k_xtrunk_demit_list, k_xtrunk_unscatter_list) read 8 contiguous bytes per
+  // trunk cell instead of the marks of every cell plus 4 scattered bytes of cslot per trunk cell — a quarter of the
+  // cells, one or two per 64-byte sector along a river.
   uint2 *tlist = nullptr;  // [ntrunk]
   u32 *tl_off = nullptr;   // [ntiles + 1] first entry of the tile
   u32 *scell = nullptr;   // [nslot]
@@ -93,7 +93,6 @@ struct ExactPlan {
 #define XTAIL_LONG 16384u
 // first of the (at most two) last rounds that are latency-bound and hold at most an eighth of the slots, or -1
 inline int xplan_tail_split(const ExactPlan *p) {
-  if (pfd_knob("PFD_TAIL_SPLIT_OFF")) return -1;
   int nb = 0, rounds[32];
   for (int b = 0; b < 32; ++b)
     if (p->b_chain[b + 1] > p->b_chain[b]) rounds[nb++] = b;

@@ -447,9 +447,6 @@ __global__ void __launch_bounds__(64) k_xtrunk_scan(Op op, const u32 *__restrict
 // chunk's values with 16-byte accesses.  The gathers of one workgroup run under the folds of the others on its CU.
 // Chains of XLONG slots or more keep their own path (k_xtrunk_pre_long + the wave-per-chain part of k_xtrunk_scan): a
 // chunk never covers their slots — it ends where the next long chain of the workgroup starts.
-#ifndef XF_ABLATE
-#define XF_ABLATE 0  // timing experiments only: 1 = no fold, 2 = no gather (wrong results)
-#endif
 // chains a round must hold to take the workgroup-per-256-chains kernels (k_xtrunk_prescan, k_xtrunk_dscan_lds);
 // PFD_TEST_FUSE_MIN: the tests run rasters of a few million cells through them
 static u32 xfuse_min_chains() {
@@ -536,11 +533,7 @@ __global__ void __launch_bounds__(256) k_xtrunk_prescan(Op op, const u32 *__rest
       Elem ev[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-#if XF_ABLATE == 2
-        ev[k] = Elem();
-#else
         ev[k] = (info[k] & XS_POST) ? op.pre_post(x[k]) : op.pre_real(x[k], info[k] & 0xFFu, (info[k] >> 8) & 0xFu);
-#endif
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const u32 i = i0 + 256u * (u32)k + tid;
@@ -555,9 +548,6 @@ __global__ void __launch_bounds__(256) k_xtrunk_prescan(Op op, const u32 *__rest
     }
     __syncthreads();
     // (2) fold
-#if XF_ABLATE == 1
-    if (cur != 0xFFFFFFFFu && cur < e) cur = endp <= e ? 0xFFFFFFFFu : e;
-#endif
     if (cur != 0xFFFFFFFFu && cur < e) {
       const u32 hi = min(endp, e) - g;
       u32 q = cur - g;
@@ -640,77 +630,14 @@ __global__ void __launch_bounds__(256) k_xtrunk_scatter(Op op, const u32 *__rest
 }
 
 // Between the rounds only the END of a chain is read from the raster (as a light upstream cell of a later round's
-// slot): the scan stores it (k_xtrunk_scan, finish).  Every other trunk cell reaches the raster in one pass in RASTER
-// order at the end (k_xtrunk_unscatter): coalesced reads of the marks and slot numbers, partial but sector-local writes —
-// the per-slot scatter in chain order paid a whole sector per 4-byte value.
+// slot): the scan stores it (k_xtrunk_scan, finish).  Every other trunk cell reaches the raster in one pass at the end,
+// over each tile's dense trunk list (round 5): 8 contiguous bytes per trunk cell — slot, local index, post slots.  The
+// per-slot scatter in chain order paid a whole sector per 4-byte value; the raster-order walk of rounds 3-4 read the
+// marks of all 4096 cells and a 16-byte quad of cslot wherever a quad held a trunk cell (along a river that is one useful
+// word per 64-byte sector).
 // (One workgroup per 64 x 64 TILE, not per strip of a raster row: a chain crosses a tile in a run of ~64 consecutive
 //  slots, so the workgroup's scattered accesses in chain order fall into a few hundred bytes per chain and the L2
 //  serves all but the first touch of a sector — a row strip meets every chain once and pays a sector per value.)
-template <class Op>
-__global__ void __launch_bounds__(256) k_xtrunk_unscatter(Op op, XTileArgs a, const typename Op::V *__restrict__ R,
-                                                          u32 s_limit = 0xFFFFFFFFu) {  // only the cells of slots below s_limit
-  const u32 tid = threadIdx.x;
-  u32 bx_, by_;
-  pfd_tile_of_block(&bx_, &by_);
-  const u32 r0 = by_ * XT, c0 = bx_ * XT;
-  u32 l4s[4], x0s[4];
-  uint4 c4s[4];
-  bool full[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const u32 l0 = 4u * tid + 1024u * j;
-    const u32 gr = r0 + (l0 >> 6), gc = c0 + (l0 & 63);
-    full[j] = gr < a.nrow && gc + 3 < a.ncol;
-    x0s[j] = gr * a.ncol + gc;
-    l4s[j] = XL_NODATA * 0x01010101u;
-    if (full[j]) {
-      __builtin_memcpy(&l4s[j], a.lh + x0s[j], 4);
-    } else if (gr < a.nrow) {
-      for (u32 b = 0; b < 4u && gc + b < a.ncol; ++b) l4s[j] = (l4s[j] & ~(0xFFu << (8 * b))) | ((u32)a.lh[x0s[j] + b] << (8 * b));
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    u32 tm = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) tm |= xl_trunk((l4s[j] >> (8 * b)) & 0xFFu) ? 1u << b : 0u;
-    c4s[j] = make_uint4(0u, 0u, 0u, 0u);
-    if (tm) {
-      if (full[j]) {
-        __builtin_memcpy(&c4s[j], a.cslot + x0s[j], 16);
-      } else {
-        u32 t[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          if ((tm >> b) & 1u) t[b] = a.cslot[x0s[j] + b];
-        c4s[j] = make_uint4(t[0], t[1], t[2], t[3]);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const u32 l4 = l4s[j];
-    u32 tm = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) tm |= xl_trunk((l4 >> (8 * b)) & 0xFFu) ? 1u << b : 0u;
-    if (!tm) continue;
-    const u32 cs[4] = {c4s[j].x, c4s[j].y, c4s[j].z, c4s[j].w};
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-      if (cs[b] >= s_limit) tm &= ~(1u << b);  // (the chains of the last rounds are scattered when they are done)
-    typename Op::V v[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)  // (the mark carries the number of post slots: the cell's value sits behind them)
-      v[b] = R[(tm >> b) & 1u ? cs[b] + ((l4 >> (8 * b)) & 7u) : 0u];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-      if ((tm >> b) & 1u) op.store(x0s[j] + b, v[b]);
-  }
-}
-
-// The same pass over the tile's dense trunk list (round 5): 8 contiguous bytes per trunk cell — slot, local index, post
-// slots — instead of the marks of all 4096 cells and a 16-byte quad of cslot wherever a quad holds a trunk cell (along a
-// river that is one useful word per 64-byte sector).
 template <class Op>
 __global__ void __launch_bounds__(256) k_xtrunk_unscatter_list(Op op, XTileArgs a, const typename Op::V *__restrict__ R,
                                                                u32 s_limit = 0xFFFFFFFFu) {
@@ -768,11 +695,6 @@ struct XStream2Guard {
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
   }
 };
-// (A/B knob: PFD_XLIST_OFF=1 walks the marks of every cell as rounds 3-4 did)
-static inline bool xlist_on() {
-  static const bool on = pfd_knob("PFD_XLIST_OFF") == nullptr;
-  return on;
-}
 // an update request (pfd_set_block_update(h, 2)) can be served: the kept sweep is this operation's, into this buffer
 static inline bool xinc_applies(pfd_raster *h, const void *out_dev, size_t tag) {
   const ExactPlan *p = (const ExactPlan *)h->xplan;
@@ -855,8 +777,8 @@ static int run_exact_up(pfd_raster *h, const Op &op, const char *name, int keep 
   Elem *E = keep ? (Elem *)p->incE : Eb.as<Elem>();
   V *R = keep ? (V *)p->incR : Rb.as<V>();
   // The last two rounds hold the main stems and their largest tributaries: a few thousand chains, the longest as long
-  // as the longest flow path, folded serially — 0.5 ms each at 30000 x 30000 with most of the chip idle.  The raster-order
-  // pass that writes the trunk cells (k_xtrunk_unscatter, bandwidth) therefore starts BESIDE them, on the handle's
+  // as the longest flow path, folded serially — 0.5 ms each at 30000 x 30000 with most of the chip idle.  The tile-order
+  // pass that writes the trunk cells (k_xtrunk_unscatter_list, bandwidth) therefore starts BESIDE them, on the handle's
   // second stream, for every chain of the earlier rounds; the chains of the last two rounds — a few per cent of the
   // slots — are scattered in chain order when they are done.
   int bsplit = xplan_tail_split(p);
@@ -875,10 +797,7 @@ static int run_exact_up(pfd_raster *h, const Op &op, const char *name, int keep 
       HIPCHK(hipEventRecord(h->ev_fork, h->stream));
       HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
       a.tlist = p->tlist, a.tl_off = p->tl_off;
-      if (xlist_on())
-        k_xtrunk_unscatter_list<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream2>>>(op, a, R, s_split);
-      else
-        k_xtrunk_unscatter<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream2>>>(op, a, R, s_split);
+      k_xtrunk_unscatter_list<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream2>>>(op, a, R, s_split);
       HIPCHK(hipEventRecord(h->ev_join, h->stream2));
       ++launches;
     }
@@ -916,10 +835,7 @@ static int run_exact_up(pfd_raster *h, const Op &op, const char *name, int keep 
   } else if (p->nslot) {
     a.cslot = p->cslot;
     a.tlist = p->tlist, a.tl_off = p->tl_off;
-    if (xlist_on())
-      k_xtrunk_unscatter_list<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream>>>(op, a, R);
-    else
-      k_xtrunk_unscatter<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream>>>(op, a, R);
+    k_xtrunk_unscatter_list<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream>>>(op, a, R);
     XDBG(h, "unscatter");
     ++launches;
   }
@@ -946,44 +862,9 @@ __global__ void __launch_bounds__(256) k_xtrunk_dpre(Op op, const u32 *__restric
   E[s] = op.dpre(x, (u32)ncode[x]);
 }
 
-// The same gather for ALL rounds at once, one workgroup per TILE (see k_xtrunk_unscatter): the operation's loads
-// run in raster order, the stores into chain order fall into the few runs of slots that cross the tile.
-template <class Op, bool LIMIT = false>
-__global__ void __launch_bounds__(256) k_xtrunk_demit(Op op, XTileArgs a, typename Op::DElem *__restrict__ E,
-                                                      u32 s_limit = 0xFFFFFFFFu) {  // LIMIT: only the slots below s_limit
-  const u32 tid = threadIdx.x;
-  u32 bx_, by_;
-  pfd_tile_of_block(&bx_, &by_);
-  const u32 r0 = by_ * XT, c0 = bx_ * XT;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const u32 l0 = 4u * tid + 1024u * j;
-    const u32 gr = r0 + (l0 >> 6), gc = c0 + (l0 & 63);
-    if (gr >= a.nrow) continue;
-    const u32 x0 = gr * a.ncol + gc;
-    u32 l4 = XL_NODATA * 0x01010101u, c4 = 0;
-    if (gc + 3 < a.ncol) {
-      __builtin_memcpy(&l4, a.lh + x0, 4);
-      __builtin_memcpy(&c4, a.ncode + x0, 4);
-    } else {
-      for (u32 b = 0; b < 4u && gc + b < a.ncol; ++b) {
-        l4 = (l4 & ~(0xFFu << (8 * b))) | ((u32)a.lh[x0 + b] << (8 * b));
-        c4 |= (u32)a.ncode[x0 + b] << (8 * b);
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      if (xl_trunk((l4 >> (8 * b)) & 0xFFu)) {
-        // (the element first, whatever the slot: its loads must not wait for the slot number)
-        const typename Op::DElem e = op.dpre(x0 + (u32)b, (c4 >> (8 * b)) & 0xFFu);
-        const u32 sl = a.cslot[x0 + b];
-        if (!LIMIT || sl < s_limit) E[sl] = e;
-      }
-    }
-  }
-}
-
-// ... and over the tile's dense trunk list (see k_xtrunk_unscatter_list)
+// The same gather for ALL rounds at once, one workgroup per TILE over the tile's dense trunk list (see
+// k_xtrunk_unscatter_list): the operation's loads follow the list, the stores into chain order fall into the few runs of
+// slots that cross the tile.
 template <class Op, bool LIMIT = false>
 __global__ void __launch_bounds__(256) k_xtrunk_demit_list(Op op, XTileArgs a, typename Op::DElem *__restrict__ E,
                                                            u32 s_limit = 0xFFFFFFFFu) {
@@ -1295,12 +1176,7 @@ __global__ void __launch_bounds__(256) k_xtrunk_dscan_lds(Op op, const u32 *__re
   const u32 tail = m ? a + m - 1u - (cl >> 29) : 0u;  // SLOT of the chain's last cell
   u32 cur = m ? pend : 0u;                        // the part [a, cur) is still to fold; 0: nothing left
   V t = V();
-#if XF_ABLATE != 3
-  if (m)
-#else
-  if (m && a == 12345u)
-#endif
-  {  // the value of the last cell: from its downstream cell — a trunk cell of a later round, final — or a pit's own
+  if (m) {  // the value of the last cell: from its downstream cell — a trunk cell of a later round, final — or a pit's own
     const u32 x = scell[tail];
     const u32 code = ncode[x];
     const Elem e = E[tail];
@@ -1326,9 +1202,6 @@ __global__ void __launch_bounds__(256) k_xtrunk_dscan_lds(Op op, const u32 *__re
       if (tid <= ((top - 1u) >> 5) - w0) sP[tid] = spost[w0 + tid];
     }
     __syncthreads();
-#if XF_ABLATE == 4
-    if (cur > lo && cur <= top && cur != 0u) cur = max(a, lo) == a ? 0u : max(a, lo);
-#endif
     if (cur > lo && cur <= top && cur != 0u) {
       const u32 stop = max(a, lo);
       for (u32 sg = cur - 4u;; sg -= 4u) {  // group of the slots sg .. sg + 3
@@ -1388,11 +1261,6 @@ __global__ void __launch_bounds__(256) k_xtrunk_dscatter(Op op, const u32 *__res
 // apply() would read from memory: gathered up front, quad by quad).  Writes every own cell once.
 // (LDS per workgroup decides how many tiles a CU overlaps, and the step loop is latency: keep it small.)
 #define XHW (XT + 2)
-#ifndef XORD_REGS
-#define XORD_REGS 0  // k_xtile_down, 1: the leaf list in registers instead of a 16 KB LDS copy with precomputed ring indices —
-                     // measured twice (round 4: per-lane range tests; round 6: uniform slices behind scalar branches,
-                     // profiles/r06_ab_ord_regs.txt) and slower both times although a tile more fits per CU: off
-#endif
 // cells whose final value is in place before the tile kernel runs: trunk cells, and the halo cells of a row block
 __device__ __forceinline__ bool xl_given(u32 m) { return xl_trunk(m) || m == XL_HALO; }
 template <class Op>
@@ -1407,9 +1275,7 @@ __global__ void __launch_bounds__(256) k_xtile_down(Op op, XTileArgs a) {
   __shared__ __attribute__((aligned(16))) Elem De[INPL ? 4 : XTC];
   // per leaf, in step order: own cell (12 bits) | ring index of its downstream cell << 12 (13 bits) | pit << 25
   // (looked up once per leaf here instead of once per step through the cell's code)
-#if !XORD_REGS
   __shared__ __attribute__((aligned(16))) u32 ord[XTC];
-#endif
   __shared__ u32 F[XTC / 32];  // one flag bit per cell, for operations whose element needs one (HAND: drain)
   __shared__ uint16_t off[XOFF];
   const u32 tid = threadIdx.x;
@@ -1510,9 +1376,7 @@ __global__ void __launch_bounds__(256) k_xtile_down(Op op, XTileArgs a) {
       }
       typename Op::DQuad dq[4];
       V vq[4][4];
-      uint4 cs4[4];
       u32 tmask[4], hmask[4];  // trunk cells / halo cells of the quad
-      const bool by_list = a.tlist != nullptr;  // (uniform) the trunk values come in through the tile's dense list below
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const u32 l0 = 4u * tid + 1024u * j;
@@ -1525,8 +1389,6 @@ __global__ void __launch_bounds__(256) k_xtile_down(Op op, XTileArgs a) {
           tmask[j] |= xl_trunk(mk) ? 1u << b : 0u;
           hmask[j] |= mk == XL_HALO ? 1u << b : 0u;
         }
-        cs4[j] = make_uint4(0u, 0u, 0u, 0u);
-        if (tmask[j] && !by_list) __builtin_memcpy(&cs4[j], a.cslot + g0, 16);  // (slot numbers of the quad's trunk cells)
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1534,14 +1396,6 @@ __global__ void __launch_bounds__(256) k_xtile_down(Op op, XTileArgs a) {
         const u32 g0 = (u32)((r0 + (l0 >> 6)) * (i64)a.ncol + c0 + (l0 & 63));
 #pragma unroll
         for (int b = 0; b < 4; ++b) vq[j][b] = V();
-        if (tmask[j] && !by_list) {  // trunk values from chain order: four loads, the marks select
-          const u32 cs[4] = {cs4[j].x, cs4[j].y, cs4[j].z, cs4[j].w};
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const V rv = Rv[(tmask[j] >> b) & 1u ? cs[b] : 0u];
-            if ((tmask[j] >> b) & 1u) vq[j][b] = rv;
-          }
-        }
         if (hmask[j]) {  // (row blocks: the given values of halo cells are in the raster)
           V hv[4];
           op.top4(g0, hv);
@@ -1571,30 +1425,28 @@ __global__ void __launch_bounds__(256) k_xtile_down(Op op, XTileArgs a) {
           } else {
             De[l0 + b] = e;
           }
-          if (!(by_list && ((tmask[j] >> b) & 1u))) val[(lr + 1) * XHW + lc + b + 1] = v;  // (a trunk cell's word: the list loop's)
+          if (!((tmask[j] >> b) & 1u)) val[(lr + 1) * XHW + lc + b + 1] = v;  // (a trunk cell's word: the list loop's)
         }
         if (Op::DTILE_FLAG && fl) atomicOr(&F[l0 >> 5], fl << (l0 & 31u));
       }
-      if (by_list) {
-        // the values of the tile's trunk cells, final in chain order: 8 contiguous bytes of the list per trunk cell instead
-        // of a 16-byte quad of cslot wherever a quad holds one (one useful word per sector along a river)
-        const u32 lb = a.tl_off[tile], le = a.tl_off[tile + 1];
-        for (u32 i0 = lb; i0 < le; i0 += 1024u) {
-          uint2 en[4];
-          V rv[4];
+      // the values of the tile's trunk cells, final in chain order: 8 contiguous bytes of the list per trunk cell instead
+      // of a 16-byte quad of cslot wherever a quad holds one (one useful word per sector along a river)
+      const u32 lb = a.tl_off[tile], le = a.tl_off[tile + 1];
+      for (u32 i0 = lb; i0 < le; i0 += 1024u) {
+        uint2 en[4];
+        V rv[4];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const u32 i = i0 + tid + 256u * (u32)k;
-            en[k] = a.tlist[i < le ? i : lb];
-          }
+        for (int k = 0; k < 4; ++k) {
+          const u32 i = i0 + tid + 256u * (u32)k;
+          en[k] = a.tlist[i < le ? i : lb];
+        }
 #pragma unroll
-          for (int k = 0; k < 4; ++k) rv[k] = Rv[en[k].x];
+        for (int k = 0; k < 4; ++k) rv[k] = Rv[en[k].x];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const u32 i = i0 + tid + 256u * (u32)k;
-            const u32 l = en[k].y & 0xFFFu;
-            if (i < le) val[((l >> 6) + 1u) * XHW + (l & 63u) + 1u] = rv[k];
-          }
+        for (int k = 0; k < 4; ++k) {
+          const u32 i = i0 + tid + 256u * (u32)k;
+          const u32 l = en[k].y & 0xFFFu;
+          if (i < le) val[((l >> 6) + 1u) * XHW + (l & 63u) + 1u] = rv[k];
         }
       }
     } else {
@@ -1604,51 +1456,6 @@ __global__ void __launch_bounds__(256) k_xtile_down(Op op, XTileArgs a) {
     general_init(mycodes);
   }
   const u32 total = off[XOFF - 1];
-#if XORD_REGS
-  // The leaf list stays in REGISTERS: list position p belongs to thread p mod 256, so a thread holds positions tid + 256 m,
-  // m = 0 .. 15, as sixteen u16 entries in eight registers — loaded once, coalesced — and the positions of a step
-  // [off[s], off[s + 1]) lie in the slices m = off[s] >> 8 .. (off[s + 1] - 1) >> 8: a range that is UNIFORM over the
-  // workgroup, so the sixteen copies of the step body sit behind scalar branches (round 4 walked all sixteen with a per-lane
-  // range test and lost 3 %).  16 KB of LDS less: HAND runs four tiles per CU instead of three, float32 down-sweeps six
-  // instead of four.  The ring index of a leaf's downstream cell is recomputed from its 3-bit direction per use.
-  // RESULT (same box, 30000^2 / C5 shape): accuflux down 9.6 -> 10.4 / 21.9 -> 23.4 ms, HAND 15.4 -> 15.4 / 34.0 -> 34.9 ms.
-  u32 en[8];
-#pragma unroll
-  for (int m = 0; m < 16; m += 2) {
-    const u32 e0 = a.tord[tile * XTC + tid + 256u * (u32)m], e1 = a.tord[tile * XTC + tid + 256u * (u32)(m + 1)];  // (zeros past `total`)
-    en[m >> 1] = e0 | (e1 << 16);
-  }
-  __syncthreads();
-  int last = 0;
-  for (int s = 1; s < XOFF - 1; ++s) last = off[s] < total ? s : last;
-  for (int s = last; s >= 0; --s) {
-    const u32 b = (u32)__builtin_amdgcn_readfirstlane((int)off[s]), e = (u32)__builtin_amdgcn_readfirstlane((int)off[s + 1]);
-    if (e > b) {
-      const u32 mlo = b >> 8, mhi = (e - 1u) >> 8;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        if ((u32)m < mlo || (u32)m > mhi) continue;  // (scalar: the whole workgroup skips the slice)
-        const u32 j = tid + 256u * (u32)m;
-        if (j >= b && j < e) {
-          const u32 w = (en[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
-          const u32 x = w & 0xFFFu, root = w >> 15;
-          const int k = (int)((w >> 12) & 7u);
-          const int dr = root ? 0 : (int)((0x101A9u >> (2 * k)) & 3u) - 1, dc = root ? 0 : (int)((0x1901Au >> (2 * k)) & 3u) - 1;
-          const u32 own = ((x >> 6) + 1) * XHW + (x & 63u) + 1;
-          const V pv = val[(u32)((int)own + dr * (int)XHW + dc)];
-          Elem el;
-          if (INPL)
-            __builtin_memcpy(&el, &val[own], sizeof(Elem));
-          else
-            el = De[x];
-          const bool f = Op::DTILE_FLAG ? ((F[x >> 5] >> (x & 31u)) & 1u) != 0 : false;
-          val[own] = root ? op.dtroot(el, f) : op.dtfold(el, f, pv);
-        }
-      }
-    }
-    __syncthreads();
-  }
-#else
   {
     uint2 o4[4];
 #pragma unroll
@@ -1687,7 +1494,6 @@ __global__ void __launch_bounds__(256) k_xtile_down(Op op, XTileArgs a) {
     }
     __syncthreads();
   }
-#endif
   u32 wmask = 0;  // (XWatch) bit 4 j + b: the value stored for that cell is one the operation watches
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -1758,11 +1564,10 @@ static int run_exact_down(pfd_raster *h, const Op &op, const char *name) {
   PFDCHK(R.alloc(std::max<size_t>((size_t)p->nslot, 1) * sizeof(V) + 64));
   XTileArgs a{(u32)h->nrow, (u32)h->ncol, p->ntc, p->lh, p->kids, h->ncode, p->tord, p->toff, p->cslot, R.p};
   a.tlist = p->tlist, a.tl_off = p->tl_off;
-  if (!xlist_on()) a.tlist = nullptr, a.tl_off = nullptr;
   // The rounds start with the main stems and their largest tributaries (the last two rounds of the layout): a few
   // thousand long chains, folded serially — 0.7 ms each for HAND at 30000 x 30000 with most of the chip idle.  Their
-  // operands are gathered in chain order first (a few per cent of the slots); the raster-order gather of everything
-  // else (k_xtrunk_demit: bandwidth) runs BESIDE those two rounds on the handle's second stream.
+  // operands are gathered in chain order first (a few per cent of the slots); the tile-order gather of everything
+  // else (k_xtrunk_demit_list: bandwidth) runs BESIDE those two rounds on the handle's second stream.
   int bsplit = xplan_tail_split(p);
   if (bsplit >= 0 && pfd_aux_stream(h) != PFD_OK) bsplit = -1;
   XStream2Guard guard2{h};  // (declared after E / R: runs before they are released)
@@ -1770,19 +1575,13 @@ static int run_exact_down(pfd_raster *h, const Op &op, const char *name) {
     const u32 s_split = (u32)p->b_slot[bsplit];
     HIPCHK(hipEventRecord(h->ev_fork, h->stream));
     HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-    if (xlist_on())
-      k_xtrunk_demit_list<Op, true><<<dim3(p->ntc, p->ntr), 256, 0, h->stream2>>>(op, a, E.as<Elem>(), s_split);
-    else
-      k_xtrunk_demit<Op, true><<<dim3(p->ntc, p->ntr), 256, 0, h->stream2>>>(op, a, E.as<Elem>(), s_split);
+    k_xtrunk_demit_list<Op, true><<<dim3(p->ntc, p->ntr), 256, 0, h->stream2>>>(op, a, E.as<Elem>(), s_split);
     HIPCHK(hipEventRecord(h->ev_join, h->stream2));
     k_xtrunk_dpre<Op><<<cdiv_u32((u32)p->nslot - s_split, 256), 256, 0, h->stream>>>(op, p->scell, p->sinfo, h->ncode, s_split,
                                                                                   (u32)p->nslot, E.as<Elem>());
     launches += 2;
   } else if (p->nslot) {  // what the folds read from memory, for every trunk cell at once (the rounds only fold)
-    if (xlist_on())
-      k_xtrunk_demit_list<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream>>>(op, a, E.as<Elem>());
-    else
-      k_xtrunk_demit<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream>>>(op, a, E.as<Elem>());
+    k_xtrunk_demit_list<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream>>>(op, a, E.as<Elem>());
     ++launches;
   }
   bool joined = bsplit < 0;

@@ -164,8 +164,7 @@ static const u32 MULTIHOP_MAX_CELLS_UP = 1u << 18;  // up-sweeps (the window for
 // ---- up-sweeps --------------------------------------------------------------------------------
 // Op: V leaf(nb) = final value of an upstream cell; V combine(x, kids, child) = value of x given
 // child(nb) for its upstream cells (called in the order the op needs); store(x, v).
-// seq positions [begin, s1) = lowest level (3 hops), [s1, s2) = middle level (2 hops), [s2, end) =
-// upper level (children final); s1 = begin / s2 = s1 when fewer levels are taken.
+// seq positions [begin, s2) = lower level (2 hops), [s2, end) = upper level (children final).
 // one level per launch (wide levels: bandwidth-bound, kept lean — the multi-hop kernel's register
 // footprint would cost occupancy)
 template <class Op>
@@ -176,10 +175,10 @@ __global__ void __launch_bounds__(256) k_sweep_up1(Op op, const u32 *__restrict_
   const u32 x = seq[pos];
   op.store(x, op.combine(x, (u32)kids_seq[pos], [&](u32 nb, int) { return op.leaf(nb); }));
 }
+// (at least 5 waves per SIMD: left alone, the allocator gives the Strahler instance 98 VGPRs — 4 waves)
 template <class Op>
-__global__ void __launch_bounds__(256) k_sweep_up(Op op, const u32 *__restrict__ seq, const u8 *__restrict__ kids_seq,
-                                                  const u64 *__restrict__ kids2_seq, const u8 *__restrict__ kids_cell,
-                                                  u32 begin, u32 s1, u32 s2, u32 end) {
+__global__ void __launch_bounds__(256, 5) k_sweep_up(Op op, const u32 *__restrict__ seq, const u8 *__restrict__ kids_seq,
+                                                     const u64 *__restrict__ kids2_seq, u32 begin, u32 s2, u32 end) {
   const u32 pos = begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (pos >= end) return;
   const u32 x = seq[pos];
@@ -190,12 +189,7 @@ __global__ void __launch_bounds__(256) k_sweep_up(Op op, const u32 *__restrict__
     return;
   }
   const u64 kids2 = kids2_seq[pos];  // child masks of the children: no lookup on the way to the grandchildren
-  if (pos >= s1) {
-    op.store(x, op.eval2(x, kids, kids2));
-  } else {
-    auto hop2 = [&](u32 nb, int) { return op.combine(nb, (u32)kids_cell[nb], leaf); };
-    op.store(x, op.combine(x, kids, [&](u32 nb, int k) { return op.combine(nb, (u32)(kids2 >> (8 * k)) & 0xFFu, hop2); }));
-  }
+  op.store(x, op.eval2(x, kids, kids2));
 }
 
 // up- to downstream: deepest level first (children final before their parent's level runs)
@@ -204,25 +198,23 @@ static int run_up(pfd_raster *h, const Op &op, const char *name) {
   PFDCHK(pfd_ensure_seq_aux(h));
   pfd_seg_begin(h, name);
   i64 launches = 0;
-  // (3 levels per launch are implemented but measured slower than 2: 35 vs 28 ms for 10003 levels with
+  // (3 levels per launch were measured slower than 2: 35 vs 28 ms for 10003 levels with
   //  nested lookups — the third hop squares the divergent fan-out — and 58 vs 25 ms with a 7x7 register
   //  window, which spills: 100 loads per thread are too many registers)
   int maxk = pfd_knob("PFD_SINGLE_HOP") ? 1 : 2;
-  if (const char *e = pfd_knob("PFD_UP_K")) maxk = std::max(1, std::min(3, atoi(e)));
   if (h->halo_top || h->halo_bot) maxk = 1;  // (a row block: the value of a halo cell is given, never recomputed)
   for (i64 l = h->n_levels - 1; l >= 0;) {
     const u32 end = (u32)h->lvl_off[l + 1];
     int k = 1;  // levels l, l-1, .. l-k+1
     while (k < maxk && l - k >= 0 && end - (u32)h->lvl_off[l - k] <= MULTIHOP_MAX_CELLS_UP) ++k;
     const u32 begin = (u32)h->lvl_off[l - k + 1];
-    const u32 s2 = (u32)h->lvl_off[l];                      // start of the upper level
-    const u32 s1 = k == 3 ? (u32)h->lvl_off[l - 1] : begin;  // start of the middle level
+    const u32 s2 = (u32)h->lvl_off[l];  // start of the upper level
     if (end > begin) {
       if (k == 1)
         k_sweep_up1<Op><<<cdiv_u32(end - begin, 256), 256, 0, h->stream>>>(op, h->seq, h->seq_kids, begin, end);
       else
         k_sweep_up<Op><<<cdiv_u32(end - begin, 256), 256, 0, h->stream>>>(op, h->seq, h->seq_kids, h->seq_kids2,
-                                                                          h->cell_kids, begin, s1, s2, end);
+                                                                          begin, s2, end);
       ++launches;
     }
     l -= k;
@@ -292,8 +284,7 @@ static int run_down(pfd_raster *h, const Op &op, const char *name) {
   PFDCHK(pfd_ensure_seq_aux(h));
   pfd_seg_begin(h, name);
   i64 launches = 0;
-  int maxk = pfd_knob("PFD_SINGLE_HOP") ? 1 : DOWN_K;
-  if (const char *e = pfd_knob("PFD_DOWN_K")) maxk = std::max(1, std::min((int)DOWN_K, atoi(e)));
+  const int maxk = pfd_knob("PFD_SINGLE_HOP") ? 1 : DOWN_K;
   for (i64 l = 0; l < h->n_levels;) {
     const u32 begin = (u32)h->lvl_off[l];
     int k = 1;
@@ -701,13 +692,10 @@ struct Strahler {
   // cell's order exceeds that of the light cells); anything else redoes the block exactly
   static constexpr bool FAST = true;
   static constexpr bool FAST_CONST = true;   // (fold_fast leaves the running value unchanged whatever the element)
-#ifndef STRAHLER_FUSE_UP
-#define STRAHLER_FUSE_UP true
-#endif
   // the fused gather + fold (k_xtrunk_prescan) LOST with the old, branchy fold (7.95 -> 8.3 ms at 30000^2: one lane per chain
   // doing a dozen dependent VALU steps per slot while its workgroup waits) and WINS with the select form: 7.65 -> 7.1 ms,
   // C5 shape 16.3 -> 13.7 ms (profiles/r06_ab_strahler_fold.txt)
-  static constexpr bool FUSE_UP = STRAHLER_FUSE_UP;
+  static constexpr bool FUSE_UP = true;
   static constexpr bool FAST_SHORT = false;  // the short chains fold exactly right away: nothing to speculate on
   __device__ __forceinline__ u32 fold(u32 t, u32 e, bool) const {
     const u32 m = e & 0xFFu;

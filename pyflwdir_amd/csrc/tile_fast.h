@@ -28,15 +28,6 @@
 #define FX_SLOT0 (2u * TCELLS)              // local pass: P byte offset of the pointer word of perimeter slot 0
 #define FX_NOBODY (FX_SLOT0 + 2u * PSL)     // ... of the root nobody asks about (pit, nodata, cell of a cycle)
 #define FX_PN (TCELLS + PSL + 8)            // P entries of the local pass
-#ifndef FY_COMBINE
-#define FY_COMBINE true
-#endif
-#ifndef FX_COMBINE
-#define FX_COMBINE true
-#endif
-#ifndef FY_LEAVES
-#define FY_LEAVES 0  // (1: the experiment of k_tile_final_fast with the in-tile leaves retired before the rounds)
-#endif
 #ifndef FXP
 #define FXP 4  // count words per perimeter slot (replicas picked by lane: a wave's atomics on one word are serialised)
 #endif
@@ -292,7 +283,7 @@ __global__ void __launch_bounds__(256) k_tile_local_fast(TileArgs a) {
     if (!fx_vote(s_flag, round, tid, lv[0] | lv[1] | lv[2] | lv[3])) break;
   }
   const u32 live = (lv[0] ? 1u : 0u) + (lv[1] ? 1u : 0u) + (lv[2] ? 1u : 0u) + (lv[3] ? 1u : 0u);
-  if ((a.ablate & 32) && tid == 0) {  // pfd_set_profiling(h, 2): rounds this tile needed (max and sum over the tiles)
+  if ((a.flags & 32) && tid == 0) {  // pfd_set_profiling(h, 2): rounds this tile needed (max and sum over the tiles)
     const unsigned long long r = (unsigned long long)min(round + 1, MAXROUNDS_TILE);
     const u32 w = (tr * a.ntc + tc) & 255u;
     atomicMax((unsigned long long *)&a.rcnt[w], r);
@@ -318,13 +309,11 @@ __global__ void __launch_bounds__(256) k_tile_local_fast(TileArgs a) {
         w[s] = x[s] < 2u * PSL ? (u32)a.weights[(size_t)(r0 + lr) * a.ncol + (size_t)(c0 + lcq + (sh[s] >> 3))] : 0u;
       }
     }
-    if (FX_COMBINE) {
-      const bool e10 = x[1] == x[0], e20 = x[2] == x[0], e21 = x[2] == x[1], e30 = x[3] == x[0], e31 = x[3] == x[1], e32 = x[3] == x[2];
-      w[0] += (e10 ? w[1] : 0u) + (e20 ? w[2] : 0u) + (e30 ? w[3] : 0u);
-      w[1] = e10 ? 0u : w[1] + ((!e20 && e21) ? w[2] : 0u) + ((!e30 && e31) ? w[3] : 0u);
-      w[2] = (e20 || e21) ? 0u : w[2] + ((!e30 && !e31 && e32) ? w[3] : 0u);
-      w[3] = (e30 || e31 || e32) ? 0u : w[3];
-    }
+    const bool e10 = x[1] == x[0], e20 = x[2] == x[0], e21 = x[2] == x[1], e30 = x[3] == x[0], e31 = x[3] == x[1], e32 = x[3] == x[2];
+    w[0] += (e10 ? w[1] : 0u) + (e20 ? w[2] : 0u) + (e30 ? w[3] : 0u);
+    w[1] = e10 ? 0u : w[1] + ((!e20 && e21) ? w[2] : 0u) + ((!e30 && e31) ? w[3] : 0u);
+    w[2] = (e20 || e21) ? 0u : w[2] + ((!e30 && !e31 && e32) ? w[3] : 0u);
+    w[3] = (e30 || e31 || e32) ? 0u : w[3];
 #pragma unroll
     for (int s = 0; s < 4; ++s)
       if (w[s]) atomicAdd((u32 *)((u8 *)A + (x[s] << (FXP == 8 ? 4 : 3)) + rep), w[s]);  // word slot * FXP + replica
@@ -461,61 +450,17 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
     for (int i = 0; i < 5; ++i) inf += ((m >> xk[i]) & 1u) ? xc[i] : 0u;
   }
   __syncthreads();
-  if (FY_LEAVES && !WEIGHTS) {
-    // EXPERIMENT (off by default, same-box A/B + SQ counters in profiles/r05_ab_tile_leaves.txt): the
-    // doubling without the in-tile leaves — cells no cell of the tile drains into, a third of them.  A leaf's count is
-    // final from the start (1) and what its ancestors get from it reaches the parent ONCE; the forest of the other cells,
-    // with the leaves absorbed, has the same counts.  Leaves are found by a mark: bit 31 of a cell's count word (never
-    // set by a count) is raised by every cell that drains into it, and by the entry that receives flow from outside.
-    // A retired leaf points at its lane's sink like a saturated cell: no instruction less, fewer LDS conflicts.
-#pragma unroll
-    for (int i = 0; i < QF * 4; ++i)
-      if (pc[i] < FY_SINK0) ((u8 *)A)[pc[i] + 3u] = 0x80u;
-    int plr = 0, plc = 0;
-    pslot_inv((int)ptid, &plr, &plc);
-    const u32 eoff = 4u * PHYS((u32)(plr * TS + plc));
-    if (inf) ((u8 *)A)[eoff + 3u] = 0x80u;
-    __syncthreads();
-    u32 leafm = 0;
-#pragma unroll
-    for (int j = 0; j < QF; ++j) {
-      const u32 l0 = 4u * tid + QSTR * j;
-      uint4 a4 = *(const uint4 *)&A[l0];
-      const u32 m4[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if (!(m4[b] >> 31) && pc[4 * j + b] < FY_SINK0) leafm |= 1u << (4 * j + b);
-      a4.x &= 0x7FFFFFFFu, a4.y &= 0x7FFFFFFFu, a4.z &= 0x7FFFFFFFu, a4.w &= 0x7FFFFFFFu;
-      *(uint4 *)&A[l0] = a4;
-    }
-    __syncthreads();
-    if (inf) atomicAdd(&A[eoff >> 2], inf);  // (an entry with inflow is marked: never a leaf; leaves that drain into it push beside this)
-#pragma unroll
-    for (int i = 0; i < QF * 4; ++i)
-      if ((leafm >> i) & 1u) atomicAdd((u32 *)((u8 *)A + pc[i]), 1u);  // (a leaf's count is its own cell: 1)
-#pragma unroll
-    for (int j = 0; j < QF; ++j) {
-      if (!((leafm >> (4 * j)) & 15u)) continue;
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if ((leafm >> (4 * j + b)) & 1u) pc[4 * j + b] = sink;
-      *(uint2 *)&P[4u * tid + QSTR * j] = make_uint2(pc[4 * j + 0] | (pc[4 * j + 1] << 16), pc[4 * j + 2] | (pc[4 * j + 3] << 16));
-      lv[j] = !(pc[4 * j + 0] & pc[4 * j + 1] & pc[4 * j + 2] & pc[4 * j + 3] & FY_SINK0);
-    }
-    __syncthreads();
-  } else {
   if (inf) {  // (one slot per perimeter cell: no two threads share a word)
     int plr, plc;
     pslot_inv((int)ptid, &plr, &plc);
     A[PHYS((u32)(plr * TS + plc))] += inf;
   }
   __syncthreads();
-  }
 
   // ---- doubling: A[J(z)] += A(z); J(z) <- J(J(z)).  A saturated cell adds to its lane's sink word --------------
   // One round reads (own counts, the pointers of the ancestors), waits for everybody's reads, then writes.  Two
   // rounds per trip with the pointer registers swapping roles, so that no register copies are needed.
-#define FY_ROUND(PC, QN, COMBINE)                                                                                       \
+#define FY_ROUND(PC, QN)                                                                                                \
   {                                                                                                               \
     u32 av[QF * 4];                                                                                              \
     _Pragma("unroll") for (int j = 0; j < QF; ++j) {                                                              \
@@ -531,21 +476,17 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
       if (lv[j]) {                                                                                                \
         /* the four cells of a quad are neighbours in a row and, after a few rounds, mostly share their target: */ \
         /* combine them in registers then (same-address LDS atomics are served one lane after the other)        */ \
-        if (COMBINE) {                                                                                            \
-          const u32 t0 = PC[4 * j], t1 = PC[4 * j + 1], t2 = PC[4 * j + 2], t3 = PC[4 * j + 3];                   \
-          u32 w0 = av[4 * j], w1 = av[4 * j + 1], w2 = av[4 * j + 2], w3 = av[4 * j + 3];                         \
-          const bool e10 = t1 == t0, e20 = t2 == t0, e21 = t2 == t1, e30 = t3 == t0, e31 = t3 == t1, e32 = t3 == t2; \
-          w0 += (e10 ? w1 : 0u) + (e20 ? w2 : 0u) + (e30 ? w3 : 0u);                                              \
-          w1 = e10 ? 0u : w1 + ((!e20 && e21) ? w2 : 0u) + ((!e30 && e31) ? w3 : 0u);                             \
-          w2 = (e20 || e21) ? 0u : w2 + ((!e30 && !e31 && e32) ? w3 : 0u);                                        \
-          w3 = (e30 || e31 || e32) ? 0u : w3;                                                                     \
-          atomicAdd((u32 *)((u8 *)A + t0), w0);                                                                   \
-          if (w1) atomicAdd((u32 *)((u8 *)A + t1), w1);                                                           \
-          if (w2) atomicAdd((u32 *)((u8 *)A + t2), w2);                                                           \
-          if (w3) atomicAdd((u32 *)((u8 *)A + t3), w3);                                                           \
-        } else {                                                                                                  \
-          _Pragma("unroll") for (int b = 0; b < 4; ++b) atomicAdd((u32 *)((u8 *)A + PC[4 * j + b]), av[4 * j + b]); \
-        }                                                                                                         \
+        const u32 t0 = PC[4 * j], t1 = PC[4 * j + 1], t2 = PC[4 * j + 2], t3 = PC[4 * j + 3];                     \
+        u32 w0 = av[4 * j], w1 = av[4 * j + 1], w2 = av[4 * j + 2], w3 = av[4 * j + 3];                           \
+        const bool e10 = t1 == t0, e20 = t2 == t0, e21 = t2 == t1, e30 = t3 == t0, e31 = t3 == t1, e32 = t3 == t2; \
+        w0 += (e10 ? w1 : 0u) + (e20 ? w2 : 0u) + (e30 ? w3 : 0u);                                                \
+        w1 = e10 ? 0u : w1 + ((!e20 && e21) ? w2 : 0u) + ((!e30 && e31) ? w3 : 0u);                               \
+        w2 = (e20 || e21) ? 0u : w2 + ((!e30 && !e31 && e32) ? w3 : 0u);                                          \
+        w3 = (e30 || e31 || e32) ? 0u : w3;                                                                       \
+        atomicAdd((u32 *)((u8 *)A + t0), w0);                                                                     \
+        if (w1) atomicAdd((u32 *)((u8 *)A + t1), w1);                                                             \
+        if (w2) atomicAdd((u32 *)((u8 *)A + t2), w2);                                                             \
+        if (w3) atomicAdd((u32 *)((u8 *)A + t3), w3);                                                             \
         lv[j] = !(QN[4 * j + 0] & QN[4 * j + 1] & QN[4 * j + 2] & QN[4 * j + 3] & FY_SINK0);                      \
         *(uint2 *)&P[4u * tid + QSTR * j] =                                                                       \
             make_uint2(QN[4 * j + 0] | (QN[4 * j + 1] << 16), QN[4 * j + 2] | (QN[4 * j + 3] << 16));             \
@@ -558,29 +499,20 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
     return v;
   };
   int round = 0;
-#ifndef FY_COPY
 #pragma nounroll
   for (; round < MAXROUNDS_TILE; round += 2) {
-    FY_ROUND(pc, qn, FY_COMBINE)
+    FY_ROUND(pc, qn)
     if (!fx_vote_n<NW>(s_flag, 0, tid, anylive())) break;
-    FY_ROUND(qn, pc, FY_COMBINE)
+    FY_ROUND(qn, pc)
     if (!fx_vote_n<NW>(s_flag, 1, tid, anylive())) {
       ++round;
       break;
     }
   }
-#else
-#pragma nounroll
-  for (; round < MAXROUNDS_TILE; ++round) {
-    FY_ROUND(pc, qn, FY_COMBINE)
-    _Pragma("unroll") for (int i = 0; i < QF * 4; ++i) pc[i] = qn[i];
-    if (!fx_vote_n<NW>(s_flag, round, tid, anylive())) break;
-  }
-#endif
 #undef FY_ROUND
   u32 live = 0;
   _Pragma("unroll") for (int j = 0; j < QF; ++j) live += lv[j] ? 1u : 0u;
-  if ((a.ablate & 32) && tid == 0) {
+  if ((a.flags & 32) && tid == 0) {
     const unsigned long long r = (unsigned long long)min(round + 1, MAXROUNDS_TILE);
     const u32 w = (tr * a.ntc + tc) & 255u;
     atomicMax((unsigned long long *)&a.rcnt[512 + w], r);

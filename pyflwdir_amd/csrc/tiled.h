@@ -112,8 +112,6 @@ struct SuperArgs {
   u32 hcap;         // super-exits per hypertile that fit in LDS (HCAP; lowered by tests via PFD_TEST_HCAP)
   u8 *sover;        // [nst] set by k_exit_lists: the supertile holds more exits than the dense form keeps in LDS
   u32 scap;         // that capacity (SCAP; lowered by tests via PFD_TEST_SCAP)
-  int ablate;       // DEVTOOLS experiments (PFD_SUPER_ABLATE): 1 skip the rounds, 2 skip the outputs, 4 no start-value gather
-  u32 st0 = 0;      // first supertile of the launch (k_exit_lists / k_boundary_records / k_super over a band of supertile rows)
 };
 
 // level-3 (hypertile = 4x4 supertiles) solve arguments; node ids k = ht*HCAP + i, i < hcnt[ht]
@@ -162,8 +160,8 @@ struct TileArgs {
   u64 *rcnt;       // pfd_set_profiling(h, 2): [4][256] doubling rounds of the tile passes (local max, local sum, final
                    // max, final sum), spread over 256 words by tile id — one same-address atomic per tile costs ~12 ns
   u64 *stamps;     // DEVTOOLS: [1024][8] cycle stamps, spread over 1024 rows against same-address atomics
-  int ablate;      // profiling knob (env PFD_TILE_ABLATE): bit0 skip doubling, bit4 cycle stamps; bit5 (set by
-                   // pfd_set_profiling(h, 2)) counts the doubling rounds per tile into ctrl[48..51]
+  int flags;       // 16: cycle stamps (DEVTOOLS, env PFD_TILE_ABLATE=16); 32 (set by pfd_set_profiling(h, 2)): count
+                   // the doubling rounds per tile into rcnt
   // the fixed-point upstream area (wide.h): when xT64 is set, the local pass of the INTERIOR tiles also sums the 64-bit
   // weights of its cells per exit (k_tile_local_fast<.., WIDE>) — the roots are in its registers anyway
   const u64 *wrow = nullptr;   // [nrow] integer part of a cell's quantised area
@@ -334,10 +332,6 @@ struct TiledRun {
   u32 nst = 0, nstc = 0, nsuper = 0, nht = 0, nhtc = 0, nhyper = 0;
   DevBuf sbbuf, l3, l4, hcntbuf, tcntbuf, iface_buf, stampbuf, soverbuf, rcntbuf, xmaskbuf, xlbuf, scountbuf, flaggedbuf, xcbbuf;
   bool fused_norm = false;  // this run's first tile pass normalises a deferred handle
-#ifndef PFD_PATCH_DEFAULT
-#define PFD_PATCH_DEFAULT 0
-#endif
-  bool use_patch = PFD_PATCH_DEFAULT != 0;  // local pass of the interior tiles: k_tile_local_patch (tile_patch.h) instead of k_tile_local_fast
   int rounds4 = 0, extra_rounds = 0;  // level-4 rounds issued without a host check / added after a miss
   bool short_of_rounds = false;
   u32 *xT = nullptr, *xrec = nullptr, *xtot = nullptr, *sxidL = nullptr, *sx_slot = nullptr,
@@ -349,15 +343,6 @@ struct TiledRun {
   size_t n3cap = 0, n4cap = 0;
   u32 *J4fin = nullptr;
   int solve_exits(const u32 *start, i64 *launches, bool cleared = false, bool edge_down = false);
-  // phase A with the supertile-local part of the exit graph (exit lists, boundary records, first supertile solve) of a BAND
-  // of supertile rows running on the handle's second stream beside the local tile pass of the next band (PFD_BANDS)
-  int phase_a_bands(int bands);
-  bool setup_only = false, up_done = false;  // solve_exits: set up the solve and return / the first supertile solve has run
-  hipEvent_t band_ev[16] = {};
-  ~TiledRun() {
-    for (hipEvent_t e : band_ev)
-      if (e) (void)hipEventDestroy(e);
-  }
   bool edge_down_now = false;
   int level3_flat(i64 *launches);
   int level3_flat_nosync(i64 *launches);

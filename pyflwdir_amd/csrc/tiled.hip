@@ -51,7 +51,7 @@
 #include "tiled.h"
 
 #define TSTAMP(slot)                                                                                        \
-  if (a.ablate & 16) {                                                                                      \
+  if (a.flags & 16) {                                                                                       \
     __syncthreads();                                                                                        \
     if (tid == 0) {                                                                                         \
       const u64 t_ = __builtin_readcyclecounter();                                                          \
@@ -271,136 +271,134 @@ __device__ __forceinline__ void tile_body(const TileArgs &a, u32 *A, uint16_t *P
     if (!(pp.x & pp.y & (pp.x >> 16) & (pp.y >> 16) & PDONE)) live |= 1u << j;
   }
   int round = 0;
-  if (!(a.ablate & 1)) {
-    // Branches are per QUAD only: inside a live quad all four cells run the same instruction
-    // stream; a saturated cell re-reads its root's pointer (its own value) and adds to a sink word,
-    // which is cheaper than four exec-mask regions per quad and round.
-    const u32 sink = (TCELLS + (tid & 63u)) * 4u;  // byte offset of this lane's sink word of A
-    const i64 r0_ = r0;                            // (the tile's first row; r0..r3 below are roots)
-    if (!FINAL) {
-      // The local pass only needs ROOTS (where does an entry's path end, which exit does a cell drain to) and
-      // the count per root (the local count of an exit) — not the count of every cell.  So it jumps pointers
-      // without carrying values, J_{k+1}(z) = J_k(J_k(z)): gather-only, half the LDS work of the value-carrying
-      // doubling, and a read that sees a pointer already advanced by its owner just jumps further (every value
-      // a pointer ever holds is an ancestor), so one barrier per round is enough.  Afterwards every cell adds
-      // its weight to its root.
-      for (; round < MAXROUNDS_TILE; ++round) {
-#pragma unroll
-        for (int j = 0; j < QPT; ++j) {
-          if (live & (1u << j)) {
-            u32 q[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) q[b] = *(const uint16_t *)((const u8 *)P + (pc[4 * j + b] & 0x1FFEu));
-#pragma unroll
-            for (int b = 0; b < 4; ++b) pc[4 * j + b] = q[b];
-            if (q[0] & q[1] & q[2] & q[3] & PDONE) live &= ~(1u << j);
-            *(uint2 *)&P[4u * tid + 1024u * j] = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
-          }
-        }
-        if (!__syncthreads_or((int)live)) break;
-      }
-      // The four cells of a quad are neighbours in a row and mostly share their root: combine them in registers
-      // first (same-address LDS atomics are served one lane per cycle).
-#pragma unroll
-      for (int j = 0; j < QPT; ++j) {
-        u32 r0 = pc[4 * j + 0], r1 = pc[4 * j + 1], r2 = pc[4 * j + 2], r3 = pc[4 * j + 3];
-        // the weights again (from the staged codes; keeping 16 of them in registers through the rounds costs a
-        // wave of occupancy): register slot s holds logical cell s ^ qs of the quad
-        u32 wq[4];
-        {
-          const u32 l0 = 4u * tid + 1024u * j;
-          const int lr = l0 >> 6, lc0 = l0 & 63;
-          const u32 qs = (tid >> 3) & 3u;
-          const u32 c4 = *(const u32 *)&CODE(lr, lc0);
-          const i64 wrow = (INT ? (i64)(r0_ + lr) : (i64)min((i64)(r0_ + lr), (i64)a.nrow - 1)) * (i64)a.ncol;
-#pragma unroll
-          for (int sl = 0; sl < 4; ++sl) {
-            const u32 b = (u32)sl ^ qs;
-            const u32 c = (c4 >> (8 * b)) & 0xFFu;
-            u32 wv = 1u;
-            if (a.weights != nullptr)
-              wv = (u32)a.weights[wrow + (INT ? (i64)(c0 + lc0) + (i64)b : min((i64)(c0 + lc0) + (i64)b, (i64)a.ncol - 1))];
-            wq[sl] = (c != D8_MV && c != D8_HALO) ? wv : 0u;
-          }
-        }
-        u32 w0 = wq[0], w1 = wq[1], w2 = wq[2], w3 = wq[3];
-        {
-          const bool e10 = r1 == r0;
-          w0 += e10 ? w1 : 0u;
-          w1 = e10 ? 0u : w1;
-          const bool e20 = r2 == r0, e21 = r2 == r1;
-          w0 += e20 ? w2 : 0u;
-          w1 += (!e20 && e21) ? w2 : 0u;
-          w2 = (e20 || e21) ? 0u : w2;
-          const bool e30 = r3 == r0, e31 = r3 == r1, e32 = r3 == r2;
-          w0 += e30 ? w3 : 0u;
-          w1 += (!e30 && e31) ? w3 : 0u;
-          w2 += (!e30 && !e31 && e32) ? w3 : 0u;
-          w3 = (e30 || e31 || e32) ? 0u : w3;
-        }
-        // (a cell that never saturated sits on or upstream of a cycle: the pass is redone by the level engine)
-        auto push = [&](u32 r, u32 w) {
-          if (!w || r < PDONE) return;
-          if (!PERIM) {
-            atomicAdd((u32 *)((u8 *)A + ((r & 0x1FFEu) << 1)), w);
-          } else {
-            // perimeter slot of the root, branch-free (pslot(), tiled.h): row 0 -> lc, row 63 -> 64 + lc,
-            // column 0 -> 127 + lr, column 63 -> 189 + lr; (x + 1) & 62 == 0 exactly for x in {0, 63}
-            const u32 L = PHYS((r & 0x1FFEu) >> 1);  // logical index of the root
-            const u32 lr = L >> 6, lc = L & 63u;
-            const bool tb = ((lr + 1u) & 62u) == 0u, lrc = ((lc + 1u) & 62u) == 0u;
-            const u32 s_tb = lc + ((lr + 1u) & 64u);
-            const u32 s_lr = 127u + lr + (((lc + 1u) & 64u) - (((lc + 1u) >> 5) & 2u));
-            const u32 ps = tb ? s_tb : s_lr;
-            if (tb || lrc) atomicAdd(&A[ps * PREP + (tid & (PREP - 1u))], w);  // (a pit inside the tile: nobody asks)
-          }
-        };
-        push(r0, w0);
-        push(r1, w1);
-        push(r2, w2);
-        push(r3, w3);
-      }
-    } else
+  // Branches are per QUAD only: inside a live quad all four cells run the same instruction
+  // stream; a saturated cell re-reads its root's pointer (its own value) and adds to a sink word,
+  // which is cheaper than four exec-mask regions per quad and round.
+  const u32 sink = (TCELLS + (tid & 63u)) * 4u;  // byte offset of this lane's sink word of A
+  const i64 r0_ = r0;                            // (the tile's first row; r0..r3 below are roots)
+  if (!FINAL) {
+    // The local pass only needs ROOTS (where does an entry's path end, which exit does a cell drain to) and
+    // the count per root (the local count of an exit) — not the count of every cell.  So it jumps pointers
+    // without carrying values, J_{k+1}(z) = J_k(J_k(z)): gather-only, half the LDS work of the value-carrying
+    // doubling, and a read that sees a pointer already advanced by its owner just jumps further (every value
+    // a pointer ever holds is an ancestor), so one barrier per round is enough.  Afterwards every cell adds
+    // its weight to its root.
     for (; round < MAXROUNDS_TILE; ++round) {
-      u32 av[QPT * 4], q[QPT * 4];
 #pragma unroll
       for (int j = 0; j < QPT; ++j) {
         if (live & (1u << j)) {
-          const uint4 a4 = *(const uint4 *)&A[4u * tid + 1024u * j];
-          av[4 * j + 0] = a4.x;
-          av[4 * j + 1] = a4.y;
-          av[4 * j + 2] = a4.z;
-          av[4 * j + 3] = a4.w;
+          u32 q[4];
 #pragma unroll
-          for (int b = 0; b < 4; ++b) q[4 * j + b] = *(const uint16_t *)((const u8 *)P + (pc[4 * j + b] & 0x1FFEu));
-        }
-      }
-      __syncthreads();  // every read of this round precedes every write of this round
+          for (int b = 0; b < 4; ++b) q[b] = *(const uint16_t *)((const u8 *)P + (pc[4 * j + b] & 0x1FFEu));
 #pragma unroll
-      for (int j = 0; j < QPT; ++j) {
-        if (live & (1u << j)) {
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const u32 p = pc[4 * j + b];
-            // a saturated cell adds to a per-lane sink word nobody reads: adding to its root would pile
-            // same-address LDS atomics onto the few roots of the tile (n-way bank conflicts).  Its pointer
-            // needs no select: a root points at itself, so a saturated pointer re-reads its own value.
-            atomicAdd((u32 *)((u8 *)A + (p >= PDONE ? sink : (p & 0x1FFEu) << 1)), av[4 * j + b]);
-            pc[4 * j + b] = q[4 * j + b];
-          }
-          if (pc[4 * j + 0] & pc[4 * j + 1] & pc[4 * j + 2] & pc[4 * j + 3] & PDONE) live &= ~(1u << j);
-          *(uint2 *)&P[4u * tid + 1024u * j] =
-              make_uint2(pc[4 * j + 0] | (pc[4 * j + 1] << 16), pc[4 * j + 2] | (pc[4 * j + 3] << 16));
+          for (int b = 0; b < 4; ++b) pc[4 * j + b] = q[b];
+          if (q[0] & q[1] & q[2] & q[3] & PDONE) live &= ~(1u << j);
+          *(uint2 *)&P[4u * tid + 1024u * j] = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
         }
       }
       if (!__syncthreads_or((int)live)) break;
     }
-    if ((a.ablate & 32) && tid == 0) {  // pfd_set_profiling(h, 2): rounds this tile needed (max and sum over the tiles)
-      const unsigned long long r = (unsigned long long)min(round + 1, MAXROUNDS_TILE);
-      const u32 w = (tr * a.ntc + tc) & 255u;
-      atomicMax((unsigned long long *)&a.rcnt[(FINAL ? 512 : 0) + w], r);
-      atomicAdd((unsigned long long *)&a.rcnt[(FINAL ? 768 : 256) + w], r);
+    // The four cells of a quad are neighbours in a row and mostly share their root: combine them in registers
+    // first (same-address LDS atomics are served one lane per cycle).
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) {
+      u32 r0 = pc[4 * j + 0], r1 = pc[4 * j + 1], r2 = pc[4 * j + 2], r3 = pc[4 * j + 3];
+      // the weights again (from the staged codes; keeping 16 of them in registers through the rounds costs a
+      // wave of occupancy): register slot s holds logical cell s ^ qs of the quad
+      u32 wq[4];
+      {
+        const u32 l0 = 4u * tid + 1024u * j;
+        const int lr = l0 >> 6, lc0 = l0 & 63;
+        const u32 qs = (tid >> 3) & 3u;
+        const u32 c4 = *(const u32 *)&CODE(lr, lc0);
+        const i64 wrow = (INT ? (i64)(r0_ + lr) : (i64)min((i64)(r0_ + lr), (i64)a.nrow - 1)) * (i64)a.ncol;
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl) {
+          const u32 b = (u32)sl ^ qs;
+          const u32 c = (c4 >> (8 * b)) & 0xFFu;
+          u32 wv = 1u;
+          if (a.weights != nullptr)
+            wv = (u32)a.weights[wrow + (INT ? (i64)(c0 + lc0) + (i64)b : min((i64)(c0 + lc0) + (i64)b, (i64)a.ncol - 1))];
+          wq[sl] = (c != D8_MV && c != D8_HALO) ? wv : 0u;
+        }
+      }
+      u32 w0 = wq[0], w1 = wq[1], w2 = wq[2], w3 = wq[3];
+      {
+        const bool e10 = r1 == r0;
+        w0 += e10 ? w1 : 0u;
+        w1 = e10 ? 0u : w1;
+        const bool e20 = r2 == r0, e21 = r2 == r1;
+        w0 += e20 ? w2 : 0u;
+        w1 += (!e20 && e21) ? w2 : 0u;
+        w2 = (e20 || e21) ? 0u : w2;
+        const bool e30 = r3 == r0, e31 = r3 == r1, e32 = r3 == r2;
+        w0 += e30 ? w3 : 0u;
+        w1 += (!e30 && e31) ? w3 : 0u;
+        w2 += (!e30 && !e31 && e32) ? w3 : 0u;
+        w3 = (e30 || e31 || e32) ? 0u : w3;
+      }
+      // (a cell that never saturated sits on or upstream of a cycle: the pass is redone by the level engine)
+      auto push = [&](u32 r, u32 w) {
+        if (!w || r < PDONE) return;
+        if (!PERIM) {
+          atomicAdd((u32 *)((u8 *)A + ((r & 0x1FFEu) << 1)), w);
+        } else {
+          // perimeter slot of the root, branch-free (pslot(), tiled.h): row 0 -> lc, row 63 -> 64 + lc,
+          // column 0 -> 127 + lr, column 63 -> 189 + lr; (x + 1) & 62 == 0 exactly for x in {0, 63}
+          const u32 L = PHYS((r & 0x1FFEu) >> 1);  // logical index of the root
+          const u32 lr = L >> 6, lc = L & 63u;
+          const bool tb = ((lr + 1u) & 62u) == 0u, lrc = ((lc + 1u) & 62u) == 0u;
+          const u32 s_tb = lc + ((lr + 1u) & 64u);
+          const u32 s_lr = 127u + lr + (((lc + 1u) & 64u) - (((lc + 1u) >> 5) & 2u));
+          const u32 ps = tb ? s_tb : s_lr;
+          if (tb || lrc) atomicAdd(&A[ps * PREP + (tid & (PREP - 1u))], w);  // (a pit inside the tile: nobody asks)
+        }
+      };
+      push(r0, w0);
+      push(r1, w1);
+      push(r2, w2);
+      push(r3, w3);
     }
+  } else
+  for (; round < MAXROUNDS_TILE; ++round) {
+    u32 av[QPT * 4], q[QPT * 4];
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) {
+      if (live & (1u << j)) {
+        const uint4 a4 = *(const uint4 *)&A[4u * tid + 1024u * j];
+        av[4 * j + 0] = a4.x;
+        av[4 * j + 1] = a4.y;
+        av[4 * j + 2] = a4.z;
+        av[4 * j + 3] = a4.w;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) q[4 * j + b] = *(const uint16_t *)((const u8 *)P + (pc[4 * j + b] & 0x1FFEu));
+      }
+    }
+    __syncthreads();  // every read of this round precedes every write of this round
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) {
+      if (live & (1u << j)) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const u32 p = pc[4 * j + b];
+          // a saturated cell adds to a per-lane sink word nobody reads: adding to its root would pile
+          // same-address LDS atomics onto the few roots of the tile (n-way bank conflicts).  Its pointer
+          // needs no select: a root points at itself, so a saturated pointer re-reads its own value.
+          atomicAdd((u32 *)((u8 *)A + (p >= PDONE ? sink : (p & 0x1FFEu) << 1)), av[4 * j + b]);
+          pc[4 * j + b] = q[4 * j + b];
+        }
+        if (pc[4 * j + 0] & pc[4 * j + 1] & pc[4 * j + 2] & pc[4 * j + 3] & PDONE) live &= ~(1u << j);
+        *(uint2 *)&P[4u * tid + 1024u * j] =
+            make_uint2(pc[4 * j + 0] | (pc[4 * j + 1] << 16), pc[4 * j + 2] | (pc[4 * j + 3] << 16));
+      }
+    }
+    if (!__syncthreads_or((int)live)) break;
+  }
+  if ((a.flags & 32) && tid == 0) {  // pfd_set_profiling(h, 2): rounds this tile needed (max and sum over the tiles)
+    const unsigned long long r = (unsigned long long)min(round + 1, MAXROUNDS_TILE);
+    const u32 w = (tr * a.ntc + tc) & 255u;
+    atomicMax((unsigned long long *)&a.rcnt[(FINAL ? 512 : 0) + w], r);
+    atomicAdd((unsigned long long *)&a.rcnt[(FINAL ? 768 : 256) + w], r);
   }
   TSTAMP(2)
   // a cell on or upstream of a cycle never saturates: count their quads (normally zero, so that no
@@ -439,7 +437,6 @@ __device__ __forceinline__ void tile_body(const TileArgs &a, u32 *A, uint16_t *P
     return;
   }
 
-  if (a.ablate & 8) return;
   // ---- perimeter records for the coarse graph ------------------------------------------------
   u32 xt = 0, xt12 = XR_NONE, inmask = 0;  // xt12: target of the exit (xr_t12)
   int plr = 0, plc = 0;
@@ -540,7 +537,6 @@ __global__ void __launch_bounds__(256) k_tile(TileArgs a) {
 #define FY_NT 256  // threads of the final pass of an interior tile (tile_fast.h; 512 = 8 waves per tile was measured: 20.5 vs 17.6 ms — tiles in flight per CU count, not waves)
 #endif
 #include "tile_fast.h"
-#include "tile_patch.h"
 
 // per-tile counts of a raw pass -> the counters k_normalise would have left in ctrl
 __global__ void __launch_bounds__(1024) k_tile_counts(const u64 *__restrict__ tcnt, u32 ntiles, u64 *ctrl) {
@@ -630,7 +626,7 @@ __global__ void __launch_bounds__(256) k_exit_lists(SuperArgs s) {
   __shared__ u32 cbase[SSL / 64];
   __shared__ u32 wsum[4];
   const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const u32 st = (blockIdx.x >> 4) + s.st0, part = blockIdx.x & 15u;  // 16 workgroups per supertile, 1024 slots (4 tiles) each
+  const u32 st = blockIdx.x >> 4, part = blockIdx.x & 15u;  // 16 workgroups per supertile, 1024 slots (4 tiles) each
   const u32 base = st << SSHIFT;
   const u32 i0 = (part << 10) + 4u * tid;  // own slots i0 .. i0 + 3
   // (unconditional: slots of tiles beyond the raster edge are allocated, never written and have no mask bit)
@@ -695,7 +691,7 @@ __global__ void __launch_bounds__(256) k_exit_lists(SuperArgs s) {
 // those super-exits itself, so every boundary cell gets one record (sb) naming its sources and the list index of the
 // exit its in-tile path reaches.  One thread per boundary cell, after k_exit_lists (xcb).
 __global__ void __launch_bounds__(256) k_boundary_records(SuperArgs s) {
-  const u32 st = (blockIdx.x >> 3) + s.st0, t = ((blockIdx.x & 7u) << 8) + threadIdx.x;
+  const u32 st = blockIdx.x >> 3, t = ((blockIdx.x & 7u) << 8) + threadIdx.x;
   u32 v = 0;
   if (t < 4u * SC - 4u) {
     u32 R, C;
@@ -756,7 +752,7 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
     if (e >= n) continue;
     const u32 w = s.xl_slot[base + e];
     u32 nx = s.xl_next[base + e];
-    const u32 t = (s.ablate & 4) ? 1u : s.xT[base + (w & (SSL - 1))];
+    const u32 t = s.xT[base + (w & (SSL - 1))];
     if (w & XL_SX) {  // a super-exit is a root; its list entry names its target instead of a next hop
       if (!FINAL) sxbits |= 1u << k;
       nx = e | SDONE;
@@ -804,7 +800,7 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
       // advanced just jumps further), and every exit adds its start value to its root afterwards.
       u32 nonroot = live;
 #pragma nounroll
-      for (int round = 0; round < ((s.ablate & 1) ? 0 : MAXROUNDS_SUPER); ++round) {
+      for (int round = 0; round < MAXROUNDS_SUPER; ++round) {
 #pragma unroll
         for (int k = 0; k < DPT; ++k) {
           if (live & (1u << k)) {
@@ -823,7 +819,7 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
       __syncthreads();
     } else {
 #pragma nounroll
-      for (int round = 0; round < ((s.ablate & 1) ? 0 : MAXROUNDS_SUPER); ++round) {
+      for (int round = 0; round < MAXROUNDS_SUPER; ++round) {
         u32 av[DPT], q[DPT];
 #pragma unroll
         for (int k = 0; k < DPT; ++k) {
@@ -845,9 +841,8 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
         if (!wg_vote<NW>(s_flag, round, tid, live != 0u)) break;
       }
     }
-    if (live && !(s.ablate & 1)) atomicAdd((unsigned long long *)&s.ctrl[T_SLIVE], 1ull);  // a cycle inside the supertile
+    if (live) atomicAdd((unsigned long long *)&s.ctrl[T_SLIVE], 1ull);  // a cycle inside the supertile
   }
-  if (s.ablate & 2) return;
   if (FINAL) {  // the total of every exit, where the tile entries it drains into will pull it
 #pragma unroll 4
     for (int k = 0; k < DPT; ++k) {
@@ -909,8 +904,8 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
 
 template <bool FINAL>
 __global__ void __launch_bounds__(SNT, SNT == 512u ? 6 : 8) k_super(SuperArgs s) {
-  if (s.sover[blockIdx.x + s.st0]) return;  // (more exits than SCAP: k_super_flagged takes it)
-  super_solve<FINAL, SCAP, SNT>(s, blockIdx.x + s.st0);
+  if (s.sover[blockIdx.x]) return;  // (more exits than SCAP: k_super_flagged takes it)
+  super_solve<FINAL, SCAP, SNT>(s, blockIdx.x);
 }
 // the supertiles k_exit_lists flagged (contrived rasters only: normally none, and a grid of this 96 KB kernel over all
 // supertiles costs 60-90 us just to find that out): a small fixed grid walks their list
@@ -1444,19 +1439,17 @@ int TiledRun::init(pfd_raster *hh, i32 *out_dev) {
   sa.flagged = flaggedbuf.as<u32>();
   if (const char *e = pfd_knob("PFD_TEST_HCAP")) sa.hcap = (u32)std::min(atoi(e), HCAP);
   if (const char *e = pfd_knob("PFD_TEST_SCAP")) sa.scap = (u32)std::min<u32>((u32)atoi(e), SCAP);
-  if (const char *e = pfd_knob("PFD_SUPER_ABLATE")) sa.ablate = atoi(e);
-  if (const char *e = pfd_knob("PFD_TILE_PATCH")) use_patch = atoi(e) != 0;
   a.stamps = nullptr;
 #ifdef PFD_DEVTOOLS
-  if (const char *e = getenv("PFD_TILE_ABLATE")) a.ablate = atoi(e);
-  if (a.ablate & 16) {
+  if (const char *e = getenv("PFD_TILE_ABLATE")) a.flags = atoi(e) & 16;
+  if (a.flags & 16) {
     PFDCHK(stampbuf.alloc(8192 * sizeof(u64)));
     a.stamps = stampbuf.as<u64>();
     HIPCHK(hipMemsetAsync(a.stamps, 0, 8192 * sizeof(u64), h->stream));
   }
 #endif
   if (h->count_rounds) {
-    a.ablate |= 32;
+    a.flags |= 32;
     PFDCHK(rcntbuf.alloc(1024 * sizeof(u64)));
     HIPCHK(hipMemsetAsync(rcntbuf.p, 0, 1024 * sizeof(u64), h->stream));
     a.rcnt = rcntbuf.as<u64>();
@@ -1614,9 +1607,7 @@ int TiledRun::solve_exits(const u32 *start, i64 *launches, bool cleared, bool ed
   flat_nosync = !is_block && sa.hmode && nht <= FLAT_MAX_HT && !(hs && atoi(hs) != 0);
   if (flat_nosync) sa.hmode = 0;
   xin3 = l3.as<u32>() + 5 * n3cap;  // (undo a rotation of level3_flat_nosync)
-  if (setup_only) return PFD_OK;  // (phase_a in bands: the caller launches the first solve band by band)
-  if (!up_done) k_super<false><<<nst, SNT, 0, h->stream>>>(sa);
-  up_done = false;
+  k_super<false><<<nst, SNT, 0, h->stream>>>(sa);
   k_super_flagged<false><<<std::min<u32>(nst, SFLAG_GRID), 1024, 0, h->stream>>>(sa);  // (normally none)
   KCHK();
   *launches += 2;
@@ -1662,10 +1653,6 @@ int TiledRun::phase_a() {
   const dim3 gridi(a.tc_hi - a.tc_lo, a.tr_hi - a.tr_lo);
   const bool have_i = gridi.x && gridi.y;
   const u32 gridf = frame_tiles(ntr, ntc, a.tr_lo, a.tr_hi, a.tc_lo, a.tc_hi);
-  if (const char *e = pfd_knob("PFD_BANDS")) {
-    const int bands = atoi(e);
-    if (bands > 1 && !is_block && have_i && !a.weights && !a.xT64 && !use_patch) return phase_a_bands(std::min(bands, 16));
-  }
   pfd_seg_begin(h, "tile_local");
   if (!h->normalised) {  // deferred handle: decode + validate + count inside the tile pass
     if (!tcntbuf.p) PFDCHK(tcntbuf.alloc((size_t)ntr * ntc * sizeof(u64)));
@@ -1674,7 +1661,6 @@ int TiledRun::phase_a() {
     if (have_i) {
       if (a.weights) k_tile_local_fast<true, true><<<gridi, 256, 0, h->stream>>>(a);
       else if (a.xT64) k_tile_local_fast<true, false, true><<<gridi, 256, 0, h->stream>>>(a);
-      else if (use_patch) k_tile_local_patch<true><<<gridi, 256, 0, h->stream>>>(a);
       else k_tile_local_fast<true, false><<<gridi, 256, 0, h->stream>>>(a);
       pfd_seg_end(h, 1);
       pfd_seg_begin(h, "tile_local_frame");
@@ -1691,7 +1677,6 @@ int TiledRun::phase_a() {
     if (have_i) {
       if (a.weights) k_tile_local_fast<false, true><<<gridi, 256, 0, h->stream>>>(a);
       else if (a.xT64) k_tile_local_fast<false, false, true><<<gridi, 256, 0, h->stream>>>(a);
-      else if (use_patch) k_tile_local_patch<false><<<gridi, 256, 0, h->stream>>>(a);
       else k_tile_local_fast<false, false><<<gridi, 256, 0, h->stream>>>(a);
       pfd_seg_end(h, 1);
       pfd_seg_begin(h, "tile_local_frame");
@@ -1721,64 +1706,6 @@ int TiledRun::phase_a() {
     launches += 3;
     KCHK();
   }
-  pfd_seg_end(h, launches);
-  return PFD_OK;
-}
-
-int TiledRun::phase_a_bands(int bands) {
-  PFDCHK(pfd_aux_stream(h));
-  const bool raw = !h->normalised;
-  const u32 gridf = frame_tiles(ntr, ntc, a.tr_lo, a.tr_hi, a.tc_lo, a.tc_hi);
-  pfd_seg_begin(h, "tile_local_frame");
-  if (raw) {
-    if (!tcntbuf.p) PFDCHK(tcntbuf.alloc((size_t)ntr * ntc * sizeof(u64)));
-    a.raw = h->raw;
-    a.tcnt = tcntbuf.as<u64>();
-    k_tile<false, true, true><<<gridf, 256, 0, h->stream>>>(a);
-    fused_norm = true;
-  } else {
-    k_tile<false, false, true><<<gridf, 256, 0, h->stream>>>(a);
-  }
-  KCHK();
-  pfd_seg_end(h, 1);
-  i64 launches = 0;
-  setup_only = true;
-  PFDCHK(solve_exits(xT, &launches, true, false));  // (pointers and modes of the solve: the first supertile solve reads them)
-  setup_only = false;
-  pfd_seg_begin(h, "tile_local");
-  const u32 nstr = cdiv_u32(ntr, SG);
-  const u32 nb_ = std::min<u32>((u32)bands, nstr);
-  i64 nl = 0;
-  for (u32 b = 0; b < nb_; ++b) {
-    const u32 sr0 = (u32)((u64)nstr * b / nb_), sr1 = (u32)((u64)nstr * (b + 1) / nb_);
-    const u32 lo = std::max(a.tr_lo, sr0 * SG), hi = std::min(a.tr_hi, sr1 * SG);
-    if (hi > lo) {
-      TileArgs ab = a;
-      ab.tr_lo = lo, ab.tr_hi = hi;
-      const dim3 g(a.tc_hi - a.tc_lo, hi - lo);
-      if (raw) k_tile_local_fast<true, false><<<g, 256, 0, h->stream>>>(ab);
-      else k_tile_local_fast<false, false><<<g, 256, 0, h->stream>>>(ab);
-      ++nl;
-    }
-    if (!band_ev[b]) HIPCHK(hipEventCreateWithFlags(&band_ev[b], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(band_ev[b], h->stream));
-    HIPCHK(hipStreamWaitEvent(h->stream2, band_ev[b], 0));
-    SuperArgs sb_ = sa;
-    sb_.st0 = sr0 * nstc;
-    const u32 nsb = (sr1 - sr0) * nstc;
-    k_exit_lists<<<nsb * 16, 256, 0, h->stream2>>>(sb_);
-    k_boundary_records<<<nsb * (SBN / 256), 256, 0, h->stream2>>>(sb_);
-    k_super<false><<<nsb, SNT, 0, h->stream2>>>(sb_);
-    launches += 3;
-  }
-  KCHK();
-  HIPCHK(hipEventRecord(h->ev_join, h->stream2));
-  HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  pfd_seg_end(h, nl);
-  if (raw) k_tile_counts<<<std::min<u32>(cdiv_u32((u64)ntr * ntc, 4096), 256u), 1024, 0, h->stream>>>(a.tcnt, ntr * ntc, h->ctrl);
-  pfd_seg_begin(h, "exit_graph");
-  up_done = true;
-  PFDCHK(solve_exits(xT, &launches, true, false));
   pfd_seg_end(h, launches);
   return PFD_OK;
 }
@@ -1839,7 +1766,7 @@ int TiledRun::phase_b_issue() {
 }
 int TiledRun::phase_b_collect(const u64 *c0, int *complete) {
   const u64 *c = c0 + 8;
-  if (a.ablate & 32) {
+  if (a.flags & 32) {
     std::vector<u64> rc(1024);
     HIPCHK(hipMemcpy(rc.data(), a.rcnt, 1024 * sizeof(u64), hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; ++k) {
@@ -1849,7 +1776,7 @@ int TiledRun::phase_b_collect(const u64 *c0, int *complete) {
     }
   }
   if (fused_norm && !h->normalised) PFDCHK(pfd_adopt_counts(h, c0));  // bad codes / no pits surface here
-  if (a.ablate & 16) {
+  if (a.flags & 16) {
     std::vector<u64> st(8192);
     HIPCHK(hipMemcpy(st.data(), a.stamps, 8192 * sizeof(u64), hipMemcpyDeviceToHost));
     u64 t[8] = {0};

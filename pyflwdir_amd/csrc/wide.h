@@ -333,9 +333,12 @@ __global__ void __launch_bounds__(NT) k_wsuper_down(SuperArgs s, const u64 *__re
 }
 
 // final pass of a tile: the doubling with 64-bit values, entries start with their own weight + the inflow they pull
-template <int NT>
-__global__ void __launch_bounds__(NT) k_wtile_final(WideArgs a) {
-  constexpr int QF = TCELLS / 4 / NT;  // quads per thread (4 with 256 threads, 2 with 512)
+// (512 threads: the 40 KB image fixes four tiles per CU either way, and eight waves per tile overlap more of the LDS round
+//  trips than four — profiles/r06f_wide_probe.txt)
+constexpr int WT_NT = 512;
+__global__ void __launch_bounds__(WT_NT) k_wtile_final(WideArgs a) {
+  constexpr int NT = WT_NT;
+  constexpr int QF = TCELLS / 4 / NT;  // quads per thread
   constexpr u32 QSTR = 4u * NT;        // cells between a thread's quads
   // (32 KB + 8 KB + the vote's flags: three tiles per CU — a fourth would need the image to be EXACTLY a quarter of the LDS,
   //  and any vote costs a few bytes; no sink words — a saturated cell issues no atomic)
@@ -563,11 +566,7 @@ int pfd_upstream_area_wide_tiled(pfd_raster *h, const u64 *wrow_dev, const u32 *
   KCHK();
   pfd_seg_end(h, launches + 1);
   pfd_seg_begin(h, "wide_tile_final");
-  // (512 threads: the 40 KB image fixes four tiles per CU either way, and eight waves per tile overlap more of the LDS
-  //  round trips than four — profiles/r06f_wide_probe.txt; PFD_WIDE_NT=256 is the other form)
-  const char *nt = pfd_knob("PFD_WIDE_NT");
-  if (nt && atoi(nt) == 256) k_wtile_final<256><<<grid, 256, 0, h->stream>>>(wa);
-  else k_wtile_final<512><<<grid, 512, 0, h->stream>>>(wa);
+  k_wtile_final<<<grid, WT_NT, 0, h->stream>>>(wa);
   KCHK();
   pfd_seg_end(h, 1);
   *complete = 1;

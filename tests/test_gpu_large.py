@@ -190,15 +190,15 @@ def test_both_level3_forms_of_a_small_raster(gpu_lib, oracle, monkeypatch, hyper
             h.close()
 
 
-@pytest.mark.parametrize("engine", ["exact", "levels", "exact:PFD_SCAN_UNFUSED", "exact:PFD_TAILS_RASTER",
-                                    "exact:PFD_ROUNDS_EARLY", "exact:PFD_DSCAN_LDS", "exact:PFD_DSCAN_GLOBAL", "exact:PFD_TEST_FUSE_MIN=1048576"])
+@pytest.mark.parametrize("engine", ["exact", "levels", "exact:PFD_SCAN_UNFUSED", "exact:PFD_DSCAN_LDS",
+                                    "exact:PFD_DSCAN_GLOBAL", "exact:PFD_TEST_FUSE_MIN=1048576"])
 def test_exact_engine_accuflux(gpu_lib, oracle, monkeypatch, engine):
     """float / int accuflux through the exact-order engine (tile leaves + heavy-chain trunk, exact.hip) and,
     forced by PFD_EXACT_LEVELS=1, through the level engine: both bit-identical to the reference's serial
     loop, with and without in-domain nodata, rasters spanning many tiles.  The exact engine in its default form
     (chain ends listed tile by tile, gather + fold of the short chains fused in k_xtrunk_prescan) and with each of the
-    round-6 choices switched the other way: the two-kernel gather / fold, the raster-ordered chain list, the "earliest
-    round" labels of the short chains, the down-fold of the short chains through LDS for every operation / for none."""
+    round-6 choices switched the other way: the two-kernel gather / fold, the down-fold of the short chains through LDS
+    for every operation / for none."""
     import pyflwdir_amd as pyflwdir
 
     O = oracle
