@@ -53,10 +53,22 @@ extern "C" {
 #define PFD_I64 3
 #define PFD_F32 4
 #define PFD_F64 5
+/* payload-only codes (pfd_fillnodata*): uint64, and the narrow integer dtypes, whose values travel WIDENED in int32
+ * lanes (data, out and halo seeds are int32 arrays holding int8 / uint8 / int16 / uint16 values) */
+#define PFD_U64 6
+#define PFD_I8 7
+#define PFD_U8 8
+#define PFD_I16 9
+#define PFD_U16 10
 
 /* accumulation direction: streams.accuflux (up) / streams.accuflux_ds (down) */
 #define PFD_UP 0
 #define PFD_DOWN 1
+
+/* fillnodata: how the upstream values meet at a confluence (direction "down") */
+#define PFD_FILL_MAX 0
+#define PFD_FILL_MIN 1
+#define PFD_FILL_SUM 2
 
 typedef struct pfd_raster pfd_raster;
 
@@ -200,6 +212,20 @@ int pfd_accuflux(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, d
  * gis_utils.area_grid, gis_utils.py:388-402 — so no n-element input has to exist or travel). */
 int pfd_accuflux_rows(pfd_raster *h, int dtype, const void *row_values, int64_t nodata_i, double nodata_f,
                       int has_nodata, int direction, int mask_invalid, void *out, int memspace);
+/* FlwdirRaster.fillnodata (reference pyflwdir/flwdir.py:360-392): a copy of `data` whose nodata cells are filled along
+ * the flow directions, over the handle's cell order (core.idxs_seq).
+ *   direction PFD_UP:   core.fillnodata_upstream (core.py:120-146) — a nodata cell takes the value of the first valid
+ *                       cell on its downstream path; `how` is ignored.
+ *   direction PFD_DOWN: core.fillnodata_downstream (core.py:149-188) — a nodata cell takes the first valid value of its
+ *                       upstream cells (descending linear index, the serial loop's order) and merges the others with
+ *                       `how` (PFD_FILL_MAX / PFD_FILL_MIN / PFD_FILL_SUM; sums wrap in the payload dtype).
+ * Valid cells, pits ("up"), nodata cells of the raster and cells that do not drain to a pit keep their value.
+ * dtype in {PFD_I32, PFD_U32, PFD_I64, PFD_U64, PFD_F32, PFD_F64} or a narrow code (PFD_I8 ... PFD_U16: int32 lanes);
+ * nodata_i (integers; the bits of the value for PFD_U64) / nodata_f (floats) / has_nodata as for pfd_accuflux:
+ * has_nodata = 0 returns a copy of `data`.  PFD_EINVAL for a bad direction or how, PFD_EUNSUPPORTED for a dtype code
+ * outside the list.  Also on general idxs_ds handles (pfd_raster_create_general), over their (installed) order. */
+int pfd_fillnodata(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
+                   int direction, int how, void *out, int memspace);
 /* OPT-IN, tolerance mode of FlwdirRaster.upstream_area(unit != "cell") on lat/lon grids (reference
  * pyflwdir/pyflwdir.py:770-801: a float64 accumulation of cell areas): `row_values` is a HOST pointer to nrow float64
  * areas, `out` receives n float64 sums, -9999 on nodata cells.  The areas are quantised to 64-bit fixed point (the
@@ -344,6 +370,15 @@ int pfd_accuflux_block(pfd_raster *h, int dtype, const void *data, int by_row, i
                        void *boundary_rows_host, int64_t *n_bad);
 int pfd_strahler_block(pfd_raster *h, const uint8_t *mask, const uint8_t *halo_seed_host, int verify, uint8_t *out,
                        int memspace, uint8_t *boundary_rows_host, int64_t *n_bad);
+/* fillnodata (reference pyflwdir/flwdir.py:360-392, core.py:120-188) of a ROW BLOCK, like pfd_accuflux_block:
+ * `halo_seed_host` holds the neighbours' results on the halo rows (2 * ncol elements of the payload's lane type).
+ * direction PFD_DOWN (an up-sweep): a halo cell that drains into the block is merged by its downstream cell in the serial
+ * loop's position; PFD_UP (a down-sweep): a halo cell the block drains into holds the neighbour's filled value.  The
+ * caller exchanges boundary rows until none changes (pyflwdir_amd/dist.py fillnodata_blocks); `verify`,
+ * `boundary_rows_host` and `n_bad` as for pfd_accuflux_block.  pfd_set_block_update does not apply. */
+int pfd_fillnodata_block(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
+                         int direction, int how, const void *halo_seed_host, int verify, void *out, int memspace,
+                         void *boundary_rows_host, int64_t *n_bad);
 /* stream_distance (reference pyflwdir/streams.py:272-315) of a row block, like pfd_accuflux_block in direction "down":
  * the halo cells the block drains into hold the neighbour's distances (`halo_seed_host`: 2 * ncol int32, or float32
  * when real_length != 0); `step_lengths` covers the rows of the block's device raster (3 * (2 * nrow - 1) floats: the

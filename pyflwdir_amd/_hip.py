@@ -19,6 +19,9 @@ PFD_I32, PFD_U32, PFD_I64, PFD_F32, PFD_F64 = 1, 2, 3, 4, 5
 _PAYLOAD_CODE = {np.dtype(np.int32): PFD_I32, np.dtype(np.int64): PFD_I64, np.dtype(np.float32): PFD_F32,
                  np.dtype(np.float64): PFD_F64}
 PFD_UP, PFD_DOWN = 0, 1
+# fillnodata payload codes beyond the five above (narrow integers travel widened in int32 lanes) and merge rules
+PFD_U64, PFD_I8, PFD_U8, PFD_I16, PFD_U16 = 6, 7, 8, 9, 10
+PFD_FILL_MAX, PFD_FILL_MIN, PFD_FILL_SUM = 0, 1, 2
 
 IDX_CODE = {np.dtype(np.int32): PFD_I32, np.dtype(np.uint32): PFD_U32, np.dtype(np.int64): PFD_I64}
 
@@ -42,6 +45,7 @@ SYMBOLS = [
     "pfd_comm_exchange_rows", "pfd_comm_allgather_host", "pfd_set_block_io", "pfd_synth_mosaic", "pfd_calib_traffic", "pfd_set_block_update",
     "pfd_reserve", "pfd_alloc_stats", "pfd_mem_info", "pfd_transfer_stats", "pfd_count_nonfinite", "pfd_floodplains_block", "pfd_trib_info_block",
     "pfd_stream_order_classic_block", "pfd_upstream_area_rows_fixed", "pfd_floodplains_block_flags",
+    "pfd_fillnodata", "pfd_fillnodata_block",
 ]
 
 _lib = None
@@ -100,6 +104,10 @@ def lib() -> C.CDLL:
         L.pfd_hand.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.pfd_accuflux_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
+        L.pfd_fillnodata.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_int]
+        L.pfd_fillnodata_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.pfd_stream_distance_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.pfd_strahler_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -534,6 +542,30 @@ class RasterHandle:
         check(lib().pfd_accuflux_block(self._h, dtype_code, ptr(data), 1 if by_row else 0, int(nodata_i), float(nodata_f),
                                        int(has_nodata), int(direction), ptr(halo_seed), 1 if verify else 0, ptr(out),
                                        memspace, ptr(brows), C.byref(bad)))
+        return brows, int(bad.value)
+
+    def fillnodata(self, data, dtype_code, nodata_i=0, nodata_f=0.0, has_nodata=1, direction=PFD_DOWN, how=PFD_FILL_MAX,
+                   out=None, memspace=PFD_HOST):
+        """fillnodata (pfd_fillnodata): ``data`` in the lane type of ``dtype_code`` (int32 lanes for the narrow codes)."""
+        if memspace == PFD_HOST:
+            out = np.empty_like(data)
+        check(lib().pfd_fillnodata(self._h, dtype_code, ptr(data), int(nodata_i), float(nodata_f), int(has_nodata),
+                                   int(direction), int(how), ptr(out), memspace))
+        return out
+
+    def fillnodata_block(self, data, dtype_code, halo_seed, out, nodata_i=0, nodata_f=0.0, has_nodata=0,
+                         direction=PFD_DOWN, how=PFD_FILL_MAX, verify=False, memspace=PFD_HOST):
+        """fillnodata of a row block whose halo cells hold ``halo_seed`` (2 * ncol values of the lane type, host); data
+        and ``out`` cover the block's device raster.  Returns (boundary rows [2, ncol], failing own cells — verify only)."""
+        brows = None
+        if not isinstance(halo_seed, DeviceBuffer):
+            halo_seed = np.ascontiguousarray(halo_seed)
+            assert halo_seed.size == 2 * self.ncol
+            brows = np.empty((2, self.ncol), halo_seed.dtype)
+        bad = C.c_int64(0)
+        check(lib().pfd_fillnodata_block(self._h, dtype_code, ptr(data), int(nodata_i), float(nodata_f), int(has_nodata),
+                                         int(direction), int(how), ptr(halo_seed), 1 if verify else 0, ptr(out), memspace,
+                                         ptr(brows), C.byref(bad)))
         return brows, int(bad.value)
 
     def stream_distance_block(self, mask, step_lengths, halo_seed, out, verify=False, memspace=PFD_HOST):

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "fill.h"
 
 int pfd_export_u32(pfd_raster *h, const u32 *src, i64 m, int idx_dtype, void *out, int memspace);  // api.hip
 
@@ -558,6 +559,57 @@ int pfd_gen_upstream_count(pfd_raster *h, const u8 *mask, int8_t *out, int memsp
   PFDCHK(o.bind(out, (size_t)h->n, memspace));
   k_gen_upcount<<<cdiv_u32(h->geo.n, 256), 256, 0, h->stream>>>(G(h)->ds, G(h)->coff, G(h)->cidx, (const u8 *)m.dev, h->geo.n,
                                                                (int8_t *)o.dev);
+  KCHK();
+  return o.finish(h->stream);
+}
+// fillnodata (reference core.fillnodata_upstream / _downstream, core.py:120-188; rules in fill.h) over the handle's
+// (possibly installed) order: "down" folds the upstream cells in descending CSR position — the serial loop's order, as
+// for accuflux — and "up" takes the downstream cell's final value
+template <class T>
+__global__ void __launch_bounds__(256) k_gen_fill_down(const u32 *__restrict__ seq, u32 begin, u32 end,
+                                                       const u32 *__restrict__ coff, const u32 *__restrict__ cidx,
+                                                       T *__restrict__ out, FillRule<T> r) {
+  const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= end) return;
+  const u32 x = seq[j];
+  T s = out[x];  // (a valid cell keeps its value: out holds the payload until the cell's own level)
+  if (!r.isnd(s)) return;
+  const u32 e0 = coff[x];
+  for (u32 e = coff[x + 1]; e > e0; --e) s = r.step(s, out[cidx[e - 1]]);
+  out[x] = s;
+}
+template <class T>
+__global__ void __launch_bounds__(256) k_gen_fill_up(const u32 *__restrict__ seq, u32 begin, u32 end,
+                                                     const u32 *__restrict__ ds, T *__restrict__ out, FillRule<T> r) {
+  const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= end) return;
+  const u32 x = seq[j], p = ds[x];
+  if (p == x) return;  // a pit keeps its value
+  out[x] = r.up(out[x], out[p]);
+}
+int pfd_gen_fillnodata(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
+                       int direction, int how, void *out, int memspace) {
+  const size_t lane = pfd_fill_lane_bytes(dtype);
+  InArg d;
+  PFDCHK(d.bind(data, (size_t)h->n * lane, memspace, h->stream));
+  OutArg o;
+  PFDCHK(o.bind(out, (size_t)h->n * lane, memspace));
+  HIPCHK(hipMemcpyAsync(o.dev, d.dev, (size_t)h->n * lane, hipMemcpyDeviceToDevice, h->stream));
+  if (!has_nodata) return o.finish(h->stream);
+  GenGraph *g = G(h);
+  auto fdown = [&](auto r) -> int {
+    typedef decltype(r.nodata) T;
+    return gen_levels(h, true, "general_fillnodata_down", [&](u32 b, u32 e, i64) {
+      k_gen_fill_down<T><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->coff, g->cidx, (T *)o.dev, r);
+    });
+  };
+  auto fup = [&](auto r) -> int {
+    typedef decltype(r.nodata) T;
+    return gen_levels(h, false, "general_fillnodata_up", [&](u32 b, u32 e, i64) {
+      k_gen_fill_up<T><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->ds, (T *)o.dev, r);
+    });
+  };
+  PFDCHK(fill_dispatch(dtype, direction == PFD_DOWN, nodata_i, nodata_f, has_nodata, how, "pfd_fillnodata", fdown, fup));
   KCHK();
   return o.finish(h->stream);
 }

@@ -12,7 +12,8 @@
 //   streams.accuflux          pyflwdir/streams.py:15-41    AccuUp
 //   streams.accuflux_ds       pyflwdir/streams.py:44-70    AccuDown
 //   streams.strahler_order    pyflwdir/streams.py:228-269  Strahler
-//   core.fillnodata_upstream  pyflwdir/core.py:120-146     Labels (basins.basins, basins.py:12-18)
+//   core.fillnodata_upstream  pyflwdir/core.py:120-146     Labels (basins.basins, basins.py:12-18), FillUp
+//   core.fillnodata_downstream pyflwdir/core.py:149-188    FillDown
 //   dem.height_above_nearest_drain  pyflwdir/dem.py:299-330  Hand
 #include <stdlib.h>
 
@@ -22,6 +23,7 @@
 
 #include "common.h"
 #include "exact.h"
+#include "fill.h"
 
 // Every ordered cell carries one byte of pre-decoded graph next to its index (built once per
 // ordering by k_seq_aux): the mask of the neighbour slots that drain into it (up-sweeps) and its
@@ -865,6 +867,152 @@ struct Flood {
   }
 };
 
+// FlwdirRaster.fillnodata, direction "down" (core.fillnodata_downstream, pyflwdir/core.py:149-188): an up-sweep.  A cell
+// whose own value is valid is a RESET — its value is its data, whatever flows in; a nodata cell starts "empty" (its own
+// value), takes the first upstream value that is not nodata and merges the rest (fill.h), children in descending
+// linear index like the serial loop.
+template <class T>
+struct FillDown {
+  typedef T V;
+  const u8 *ncode;
+  Geo g;
+  const T *data;
+  T *out;
+  FillRule<T> r;
+  const u8 *halo_raw;  // row blocks: the given D8 codes of the halo rows (top, bottom); null on a whole raster
+  __device__ __forceinline__ T leaf(u32 nb) const { return out[nb]; }
+  template <class F>
+  __device__ __forceinline__ T combine(u32 x, u32 kids, F child) const {
+    T s = data[x];
+    if (!r.isnd(s)) return s;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int k = PFD_SLOT_DESC[q];
+      if (kids & (1u << k)) s = r.step(s, child(nb_of(g, x, k), k));
+    }
+    return s;
+  }
+  __device__ __forceinline__ T eval2(u32 x, u32 kids, u64 kids2) const {
+    T W[25], Dw[25];
+    load_window5(out, g, x, W);
+    load_window5(data, g, x, Dw);
+    T s = Dw[12];
+    if (!r.isnd(s)) return s;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int k = slot_desc(q);
+      if (kids & (1u << k)) {
+        const u32 kk = (u32)(kids2 >> (8 * k)) & 0xFFu;
+        T a = Dw[win_idx(k, -1)];
+        if (r.isnd(a)) {
+#pragma unroll
+          for (int q2 = 0; q2 < 8; ++q2) {
+            const int k2 = slot_desc(q2);
+            if (kk & (1u << k2)) a = r.step(a, W[win_idx(k, k2)]);
+          }
+        }
+        s = r.step(s, a);
+      }
+    }
+    return s;
+  }
+  __device__ __forceinline__ void store(u32 x, T v) const { out[x] = v; }
+  // ---- exact-order engine (exact_sweep.h) ----
+  // element of a real slot: reset = the cell is valid (v = its data), else v = the cell's nodata value with the light
+  // upstream cells before the heavy one folded in; of a post slot: reset = the cell it drains into is valid (the slot
+  // passes the running value through), else v = the light upstream cell's value
+  struct Elem {
+    T v;
+    u32 reset;
+  };
+  typedef T LV;
+  __device__ __forceinline__ T tile_init(u32 x, bool) const { return data[x]; }
+  __device__ __forceinline__ T tile_combine(u32 l, u32 kids, const T *val) const {
+    T s = val[l];  // (still the cell's own value: a cell is combined once)
+    if (!r.isnd(s)) return s;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int k = slot_desc(q);
+      if (kids & (1u << k)) s = r.step(s, val[(int)l + slot_dr(k) * XT + slot_dc(k)]);
+    }
+    return s;
+  }
+  __device__ __forceinline__ void tile_store(u32 x, T v) const { out[x] = v; }
+  static constexpr bool NEEDS_NODATA = false;
+  __device__ __forceinline__ void tile_init4(u32 x0, u32, T (&v)[4]) const { __builtin_memcpy(v, data + x0, 4 * sizeof(T)); }
+  __device__ __forceinline__ void tile_store4(u32 x0, const T (&v)[4]) const { __builtin_memcpy(out + x0, v, 4 * sizeof(T)); }
+  __device__ __forceinline__ Elem pre_real(u32 x, u32 kids, u32 hs) const {
+    T s = data[x];
+    if (!r.isnd(s)) return Elem{s, 1u};
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int k = slot_desc(q);
+      if ((u32)k == hs) break;
+      if (kids & (1u << k)) s = r.step(s, out[nb_of(g, x, k)]);
+    }
+    return Elem{s, 0u};
+  }
+  __device__ __forceinline__ Elem pre_post(u32 child) const {
+    u32 c = ncode[child];
+    if (c == D8_HALO) {  // (a halo cell of a row block: its direction is in the given codes)
+      const u32 row = geo_row(g, child);
+      c = halo_raw[(row == 0 ? 0u : g.ncol) + (child - row * g.ncol)];
+    }
+    return Elem{out[child], r.isnd(data[d8_down(g, child, c)]) ? 0u : 1u};
+  }
+  __device__ __forceinline__ T first(const Elem &e) const { return e.v; }
+  __device__ __forceinline__ T fold(T t, const Elem &e, bool post) const {
+    if (post) return e.reset ? t : r.step(t, e.v);
+    return e.reset ? e.v : r.step(e.v, t);
+  }
+  static constexpr bool FAST = false;
+  static constexpr bool FAST_CONST = false;
+  static constexpr bool FUSE_UP = true;
+  static constexpr bool FAST_SHORT = false;
+  __device__ __forceinline__ bool special(T, const Elem &) const { return true; }
+  __device__ __forceinline__ T fold_fast(T t, const Elem &) const { return t; }
+};
+
+// FlwdirRaster.fillnodata, direction "up" (core.fillnodata_upstream, pyflwdir/core.py:120-146): a down-sweep.  A nodata
+// cell takes its downstream cell's final value unless that is nodata too: the first valid value on its path, or its
+// own.  A pit keeps its value.
+template <class T>
+struct FillUp {
+  typedef T V;
+  const u8 *ncode;
+  Geo g;
+  const T *data;
+  T *out;
+  FillRule<T> r;
+  __device__ __forceinline__ T top(u32 p) const { return out[p]; }
+  __device__ __forceinline__ T apply(u32 x, u32, bool root, T pv) const { return root ? data[x] : r.up(data[x], pv); }
+  __device__ __forceinline__ void store(u32 x, T v) const { out[x] = v; }
+  // ---- exact-order engine ----
+  typedef T DElem;
+  __device__ __forceinline__ T dnodata(u32 x) const { return data[x]; }
+  __device__ __forceinline__ void dstore4(u32 x0, const T (&v)[4]) const { __builtin_memcpy(out + x0, v, 4 * sizeof(T)); }
+  __device__ __forceinline__ T dpre(u32 x, u32) const { return data[x]; }
+  __device__ __forceinline__ T droot(T e) const { return e; }
+  __device__ __forceinline__ T dfold(T e, T pv) const { return r.up(e, pv); }
+  typedef DElem DTile;
+  static constexpr bool DTILE_FLAG = false;
+  static constexpr bool DTILE4 = true;
+  static constexpr bool DSCAN_LDS = false;
+  struct DQuad {
+    T d[4];
+  };
+  __device__ __forceinline__ void dtile4_load(u32 x0, u32, DQuad &q) const { __builtin_memcpy(q.d, data + x0, 4 * sizeof(T)); }
+  __device__ __forceinline__ T dtile4_get(const DQuad &q, int b, bool &) const { return q.d[b]; }
+  __device__ __forceinline__ DElem dtile(u32 x, u32 code, bool &) const { return dpre(x, code); }
+  __device__ __forceinline__ T dtroot(DElem e, bool) const { return droot(e); }
+  __device__ __forceinline__ T dtfold(DElem e, bool, T pv) const { return dfold(e, pv); }
+  __device__ __forceinline__ void top4(u32 x0, T (&v)[4]) const { __builtin_memcpy(v, out + x0, 4 * sizeof(T)); }
+  static constexpr bool FAST = false;
+  static constexpr bool FAST_CONST = false;
+  __device__ __forceinline__ bool dspecial(T, T) const { return true; }
+  __device__ __forceinline__ T dfold_fast(T, T pv) const { return pv; }
+};
+
 #include "exact_sweep.h"
 
 // up-/down-sweep of an operation: the exact-order engine when the raster has a plan (no cycles, whole
@@ -1123,6 +1271,63 @@ extern "C" int pfd_accuflux_rows(pfd_raster *h, int dtype, const void *row_value
                                  int has_nodata, int direction, int mask_invalid, void *out, int memspace) {
   return accuflux_impl(h, dtype, row_values, true, nodata_i, nodata_f, has_nodata, direction, mask_invalid, out,
                        memspace);
+}
+
+// ---- fillnodata (reference pyflwdir/flwdir.py:360-392; core.fillnodata_upstream / _downstream, core.py:120-188) ----
+size_t pfd_fill_lane_bytes(int dtype) {  // 0: not a fillnodata payload code
+  switch (dtype) {
+    case PFD_I32: case PFD_U32: case PFD_I8: case PFD_U8: case PFD_I16: case PFD_U16: case PFD_F32: return 4;
+    case PFD_I64: case PFD_U64: case PFD_F64: return 8;
+    default: return 0;
+  }
+}
+static int fill_check_args(const void *data, const void *out, int direction, int how, const char *what) {
+  if (!data || !out || (direction != PFD_UP && direction != PFD_DOWN) ||
+      (direction == PFD_DOWN && how != PFD_FILL_MAX && how != PFD_FILL_MIN && how != PFD_FILL_SUM)) {
+    pfd_set_error("%s: bad arguments", what);
+    return PFD_EINVAL;
+  }
+  return PFD_OK;
+}
+
+extern "C" int pfd_fillnodata(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
+                              int direction, int how, void *out, int memspace) {
+  PFDCHK(pfd_check_handle(h));
+  PFDCHK(fill_check_args(data, out, direction, how, "pfd_fillnodata"));
+  const size_t lane = pfd_fill_lane_bytes(dtype);
+  if (!lane) {
+    pfd_set_error("pfd_fillnodata: unsupported payload dtype code %d", dtype);
+    return PFD_EUNSUPPORTED;
+  }
+  pfd_seg_clear(h);
+  if (h->gen) return pfd_gen_fillnodata(h, dtype, data, nodata_i, nodata_f, has_nodata, direction, how, out, memspace);
+  InArg d;
+  PFDCHK(d.bind(data, (size_t)h->n * lane, memspace, h->stream));
+  OutArg o;
+  PFDCHK(o.bind(out, (size_t)h->n * lane, memspace));
+  if (!has_nodata) {  // nothing compares equal to nodata: a copy (no ordering needed)
+    HIPCHK(hipMemcpyAsync(o.dev, d.dev, (size_t)h->n * lane, hipMemcpyDeviceToDevice, h->stream));
+    return o.finish(h->stream);
+  }
+  PFDCHK(ensure_sweep_structure(h));
+  // (the exact engine's tile pass writes every cell; the level engine leaves the cells off the sequence alone)
+  if (h->xplan_state != 1) {
+    pfd_seg_begin(h, "init");
+    HIPCHK(hipMemcpyAsync(o.dev, d.dev, (size_t)h->n * lane, hipMemcpyDeviceToDevice, h->stream));
+    pfd_seg_end(h, 1);
+  }
+  auto fdown = [&](auto r) -> int {
+    typedef decltype(r.nodata) T;
+    FillDown<T> op{h->ncode, h->geo, (const T *)d.dev, (T *)o.dev, r, nullptr};
+    return sweep_up(h, op, "sweep_fillnodata_down", "exact_fillnodata_down");
+  };
+  auto fup = [&](auto r) -> int {
+    typedef decltype(r.nodata) T;
+    FillUp<T> op{h->ncode, h->geo, (const T *)d.dev, (T *)o.dev, r};
+    return sweep_down(h, op, "sweep_fillnodata_up", "exact_fillnodata_up");
+  };
+  PFDCHK(fill_dispatch(dtype, direction == PFD_DOWN, nodata_i, nodata_f, has_nodata, how, "pfd_fillnodata", fdown, fup));
+  return o.finish(h->stream);
 }
 
 extern "C" int pfd_strahler(pfd_raster *h, const uint8_t *mask, uint8_t *out, int memspace) {
@@ -1571,6 +1776,8 @@ __device__ __forceinline__ u64 bits_of(float v) { return (u64)__float_as_uint(v)
 __device__ __forceinline__ u64 bits_of(i64 v) { return (u64)v; }
 __device__ __forceinline__ u64 bits_of(i32 v) { return (u64)(u32)v; }
 __device__ __forceinline__ u64 bits_of(u8 v) { return (u64)v; }
+__device__ __forceinline__ u64 bits_of(u32 v) { return (u64)v; }
+__device__ __forceinline__ u64 bits_of(u64 v) { return v; }
 template <class T>
 __device__ __forceinline__ bool bits_equal(const T &a, const T &b) { return bits_of(a) == bits_of(b); }
 __device__ __forceinline__ bool bits_equal(const FloodV &a, const FloodV &b) {  // (the padding word carries nothing)
@@ -1794,6 +2001,52 @@ extern "C" int pfd_accuflux_block(pfd_raster *h, int dtype, const void *data, in
       pfd_set_error("pfd_accuflux_block: unsupported payload dtype code %d", dtype);
       return PFD_EUNSUPPORTED;
   }
+}
+extern "C" int pfd_fillnodata_block(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f,
+                                    int has_nodata, int direction, int how, const void *halo_seed_host, int verify,
+                                    void *out, int memspace, void *boundary_rows_host, int64_t *n_bad) {
+  PFDCHK(up_block_prepare(h, "pfd_fillnodata_block"));
+  PFDCHK(fill_check_args(data, out, direction, how, "pfd_fillnodata_block"));
+  if (!halo_seed_host) {
+    pfd_set_error("pfd_fillnodata_block: bad arguments");
+    return PFD_EINVAL;
+  }
+  const size_t lane = pfd_fill_lane_bytes(dtype);
+  if (!lane) {
+    pfd_set_error("pfd_fillnodata_block: unsupported payload dtype code %d", dtype);
+    return PFD_EUNSUPPORTED;
+  }
+  if (!verify && h->block_update != 0) {  // (no kept sweep: a fill sweeps the block each time)
+    pfd_set_error("pfd_fillnodata_block: pfd_set_block_update does not apply");
+    return PFD_EINVAL;
+  }
+  InArg d, sd;
+  PFDCHK(d.bind(data, (size_t)h->n * lane, memspace, h->stream));
+  PFDCHK(sd.bind(halo_seed_host, 2 * (size_t)h->ncol * lane, h->block_seed_space, h->stream));
+  OutArg o;
+  PFDCHK(o.bind(out, (size_t)h->n * lane, memspace));
+  if (verify && memspace == PFD_HOST)
+    HIPCHK(hipMemcpyAsync(o.dev, out, (size_t)h->n * lane, hipMemcpyHostToDevice, h->stream));
+  if (!verify) {
+    pfd_seg_begin(h, "init");
+    HIPCHK(hipMemcpyAsync(o.dev, d.dev, (size_t)h->n * lane, hipMemcpyDeviceToDevice, h->stream));
+    pfd_seg_end(h, 1);
+  }
+  auto fdown = [&](auto r) -> int {
+    typedef decltype(r.nodata) T;
+    FillDown<T> op{h->ncode, h->geo, (const T *)d.dev, (T *)o.dev, r, h->halo_raw};
+    return up_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)boundary_rows_host, n_bad,
+                        "sweep_fillnodata_down_block");
+  };
+  auto fup = [&](auto r) -> int {
+    typedef decltype(r.nodata) T;
+    FillUp<T> op{h->ncode, h->geo, (const T *)d.dev, (T *)o.dev, r};
+    return down_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)boundary_rows_host, n_bad,
+                          "sweep_fillnodata_up_block");
+  };
+  PFDCHK(fill_dispatch(dtype, direction == PFD_DOWN, nodata_i, nodata_f, has_nodata, how, "pfd_fillnodata_block", fdown,
+                       fup));
+  return verify ? PFD_OK : o.finish(h->stream);
 }
 extern "C" int pfd_strahler_block(pfd_raster *h, const uint8_t *mask, const uint8_t *halo_seed_host, int verify, uint8_t *out,
                                   int memspace, uint8_t *boundary_rows_host, int64_t *n_bad) {

@@ -351,13 +351,14 @@ class _UpBlock(_SeedGate):
     result stay in HBM; only the two boundary rows travel."""
 
     def __init__(self, handle, kind, dtype, payload=None, by_row=False, nodata=(0, 0.0, 0), mask=None, direction=_hip.PFD_UP,
-                 out=None):
+                 out=None, code=None, how=_hip.PFD_FILL_MAX):
         self.h, self.kind, self.dtype, self.by_row, self.nodata = handle, kind, np.dtype(dtype), by_row, nodata
         self.direction = direction
+        self.code, self.how = code, how  # (fillnodata: the payload code — narrow dtypes travel in int32 lanes — and merge rule)
         ncol, dev = handle.ncol, handle.device
         self.nrows_dev = handle.nrow + sum(handle.halo)
         self.payload = self.mask = None
-        if kind == "accuflux":
+        if kind in ("accuflux", "fillnodata"):
             payload = np.ascontiguousarray(payload, dtype=self.dtype)
             assert payload.size == (self.nrows_dev if by_row else self.nrows_dev * ncol)
             self.payload = payload if by_row else _hip.DeviceBuffer(payload.nbytes, dev).upload(payload)
@@ -388,6 +389,10 @@ class _UpBlock(_SeedGate):
             return self.h.accuflux_block(self.payload, _hip._PAYLOAD_CODE[self.dtype], seed, self.out, nd_i, nd_f, has_nd,
                                          by_row=self.by_row, verify=verify, memspace=_hip.PFD_DEVICE,
                                          direction=self.direction)
+        if self.kind == "fillnodata":
+            nd_i, nd_f, has_nd = self.nodata
+            return self.h.fillnodata_block(self.payload, self.code, seed, self.out, nd_i, nd_f, has_nd,
+                                           direction=self.direction, how=self.how, verify=verify, memspace=_hip.PFD_DEVICE)
         if self.kind == "distance":
             return self.h.stream_distance_block(self.mask, self.payload, seed, self.out, verify=verify, memspace=_hip.PFD_DEVICE)
         return self.h.strahler_block(self.mask, seed, self.out, verify=verify, memspace=_hip.PFD_DEVICE)
@@ -501,6 +506,40 @@ def accuflux_blocks(d8: np.ndarray, nblocks: int, data, nodata_args=(0, 0.0, 0),
     blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks),
                                                                down=direction != "up"),
                         _stream_blocks(d8.size, (1 if by_row else 2) * dtype.itemsize + 28, devices))
+    try:
+        out = _result_array(blocks, rows, ncol, dtype)
+        it, bad = _up_blocks_run(blocks, ncol, dtype, max_iter=max_iter, verify=verify)
+        return _collect(blocks, rows, out), it, bad
+    finally:
+        for blk in blocks:
+            blk.close()
+
+
+def fillnodata_blocks(d8: np.ndarray, nblocks: int, data, code, nodata_args=(0, 0.0, 0), direction="down",
+                      how=_hip.PFD_FILL_MAX, devices=None, verify=False, max_iter=MAX_ROUNDS):
+    """``fillnodata(data, nodata, direction, how)`` (reference pyflwdir/flwdir.py:360-392, core.py:120-188) of a host
+    raster computed as ``nblocks`` row blocks held by this one process (rasters beyond 2**32 - 2 cells).  ``data``: the
+    payload raster in the lane type of ``code`` (int32 for the narrow codes); ``nodata_args`` as raster._payload_args
+    returns them.  Direction "down" is an up-sweep like accuflux "up": a halo cell draining into a block is merged by its
+    downstream cell in the serial loop's position.  Direction "up" is a down-sweep like accuflux "down": the halo cell
+    below holds the neighbour's filled value.  Both exchange boundary rows until they are stable (_up_blocks_run).
+    Returns (result, rounds, bad cells or None)."""
+    d8 = np.ascontiguousarray(d8, dtype=np.uint8)
+    nrow, ncol = d8.shape
+    data = np.asarray(data).reshape(nrow, ncol)
+    dtype = data.dtype
+    devices = devices or [0] * nblocks
+    rows = block_rows(nrow, nblocks)
+    dirc = _hip.PFD_UP if direction == "up" else _hip.PFD_DOWN
+
+    def make(b):
+        a, e = block_slice(nrow, nblocks, b)
+        h = _hip.RasterHandle(d8[a:e], rows[b][1] - rows[b][0], ncol, device=devices[b], halo=halo_of(b, nblocks))
+        return _UpBlock(h, "fillnodata", dtype, payload=data[a:e], nodata=nodata_args, direction=dirc, code=code, how=how)
+
+    blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks),
+                                                               down=direction == "up"),
+                        _stream_blocks(d8.size, 2 * dtype.itemsize + 28, devices))
     try:
         out = _result_array(blocks, rows, ncol, dtype)
         it, bad = _up_blocks_run(blocks, ncol, dtype, max_iter=max_iter, verify=verify)

@@ -8,6 +8,7 @@ Mirrors (names, argument meaning, return conventions, error messages):
 * ``FlwdirRaster.__init__``            reference pyflwdir/pyflwdir.py:211-273, pyflwdir/flwdir.py:72-127
 * ``upstream_area``                    reference pyflwdir/pyflwdir.py:770-801
 * ``accuflux``                         reference pyflwdir/flwdir.py:567-602
+* ``fillnodata``                       reference pyflwdir/flwdir.py:360-392
 * ``stream_order``                     reference pyflwdir/flwdir.py:508-547
 * ``basins``                           reference pyflwdir/pyflwdir.py:564-599
 * ``hand``                             reference pyflwdir/pyflwdir.py:1485-1511
@@ -676,6 +677,37 @@ class FlwdirRaster(object):
                                       "wraps around there); pass the data as int32 / int64")
         return out.astype(dt)
 
+    def fillnodata(self, data, nodata, direction="down", how="max"):
+        """Fill the cells of ``data`` that hold ``nodata`` from the nearest valid cell up- or downstream; reference
+        pyflwdir/flwdir.py:360-392 (core.fillnodata_upstream / fillnodata_downstream, core.py:120-188).  ``"up"``: a
+        nodata cell takes the value of the first valid cell on its downstream path; ``"down"``: a nodata cell takes the
+        values of its valid (or filled) upstream cells, merged at confluences with ``how`` ("max", "min" or "sum", in the
+        serial loop's order, sums wrapping in the payload dtype).  Cells off the reference's ``idxs_seq`` are left as they
+        are.  One handle, the general engine, or row blocks beyond 2**32 - 2 cells."""
+        direction = str(direction).lower()
+        if direction not in ("up", "down"):
+            raise ValueError(f'Unknown flow direction: {direction}, select from ["up", "down"].')
+        if direction == "down" and how not in ["min", "max", "sum"]:  # (the reference's assert, as the same exception type)
+            raise AssertionError(f'Unknown method: {how}, select from ["min", "max", "sum"].')
+        data = np.asarray(data)
+        flat = self._check_data(data, "data")
+        lanes, code, nd_i, nd_f, has_nd = _fill_args(flat, nodata)
+        hw = {"max": _hip.PFD_FILL_MAX, "min": _hip.PFD_FILL_MIN, "sum": _hip.PFD_FILL_SUM}[how] if direction == "down" \
+            else _hip.PFD_FILL_MAX
+        nb = self._row_blocks_needed()
+        if nb > 1:  # beyond 32-bit cell indices: seeded row blocks (pyflwdir_amd/dist.py), bit-identical
+            from . import dist
+
+            self._refuse_cycles_in_blocks("fillnodata")
+            out = dist.fillnodata_blocks(self._d8, nb, lanes, code, (nd_i, nd_f, has_nd), direction=direction, how=hw)[0]
+        else:
+            dirc = _hip.PFD_UP if direction == "up" else _hip.PFD_DOWN
+            out = self._h.fillnodata(lanes, code, nodata_i=nd_i, nodata_f=nd_f, has_nodata=has_nd, direction=dirc, how=hw)
+        out = out.ravel()
+        if out.dtype != flat.dtype:  # (narrow integers: back from their int32 lanes, every value in range)
+            out = out.astype(flat.dtype)
+        return out.reshape(data.shape)
+
     def upstream_sum(self, data, mv=-9999):
         """Sum of the values of the cells directly upstream; reference pyflwdir/flwdir.py:412-433,
         pyflwdir/arithmetics.py:147-169 (incl. where its serial loop writes the missing value)."""
@@ -1150,3 +1182,38 @@ def _payload_args(flat, nodata):
     if dt.kind == "u":  # reinterpret as the signed kernel type
         nd = int(np.array([nd], dtype=dt).view(view.dtype)[0])
     return view, code, nd, 0.0, 1
+
+
+_FILL_CODES = {np.dtype(np.int8): _hip.PFD_I8, np.dtype(np.uint8): _hip.PFD_U8, np.dtype(np.int16): _hip.PFD_I16,
+               np.dtype(np.uint16): _hip.PFD_U16, np.dtype(np.int32): _hip.PFD_I32, np.dtype(np.uint32): _hip.PFD_U32,
+               np.dtype(np.int64): _hip.PFD_I64, np.dtype(np.uint64): _hip.PFD_U64, np.dtype(np.float32): _hip.PFD_F32,
+               np.dtype(np.float64): _hip.PFD_F64}
+
+
+def _fill_args(flat, nodata):
+    """fillnodata payload -> (lanes, dtype code, nodata_i, nodata_f, has_nodata) for pfd_fillnodata.  Narrow integers
+    travel widened to int32 lanes (the device wraps their sums in the narrow dtype); unsigned ones keep their own code, so
+    that max / min compare unsigned.  ``has_nodata`` is 0 when no element can compare equal to ``nodata`` (as in
+    _payload_args): the result is then a copy of the payload."""
+    dt = flat.dtype
+    if dt not in _FILL_CODES:
+        raise NotImplementedError(f"fillnodata: payload dtype {dt} is not supported on the HIP path "
+                                  "(supported: int8 ... int64, uint8 ... uint64, float32, float64)")
+    code = _FILL_CODES[dt]
+    lanes = np.ascontiguousarray(flat.astype(np.int32) if dt.itemsize < 4 else flat)
+    if dt.kind == "f":
+        nd = float(nodata)
+        if nd != nd:
+            return lanes, code, 0, 0.0, 0
+        return lanes, code, 0, float(dt.type(nd)), 1
+    info = np.iinfo(dt)
+    try:
+        integral = float(nodata) == int(nodata)
+    except (OverflowError, ValueError, TypeError):
+        integral = False
+    if not integral or not (info.min <= int(nodata) <= info.max):
+        return lanes, code, 0, 0.0, 0
+    nd = int(nodata)
+    if nd > np.iinfo(np.int64).max:  # (uint64: the bits of the value)
+        nd -= 1 << 64
+    return lanes, code, nd, 0.0, 1

@@ -54,6 +54,30 @@ print("   warm segments", [(s['name'], round(s['ms'], 2), s['launches']) for s i
 h.set_profiling(False)
 timed("accuflux f32 (up)", lambda: h.accuflux(w, _hip.PFD_F32, nodata_f=-9999.0, out=out4, memspace=_hip.PFD_DEVICE))
 timed("accuflux f32 (down)", lambda: h.accuflux(w, _hip.PFD_F32, nodata_f=-9999.0, direction=_hip.PFD_DOWN, out=out4, memspace=_hip.PFD_DEVICE))
+# fillnodata: one cell in seven holds a value, the rest -9999 (gauges / widths carried along the network)
+wf = np.full(n, -9999.0, np.float32)
+wf[::7] = (np.arange(wf[::7].size) % 1000 + 1).astype(np.float32)
+fnd = _hip.DeviceBuffer(n * 4).upload(wf)
+del wf
+hf = _hip.RasterHandle(d8, nrow, ncol, device=0, memspace=_hip.PFD_DEVICE)
+sync(); t0 = time.perf_counter()
+hf.fillnodata(fnd, _hip.PFD_F32, nodata_f=-9999.0, direction=_hip.PFD_DOWN, how=_hip.PFD_FILL_MAX, out=out4, memspace=_hip.PFD_DEVICE)
+sync(); t1 = time.perf_counter()
+hf.close(); del hf
+print(f"{'first fillnodata down':22s} {1e3*(t1-t0):10.2f} ms  (fresh handle: builds the exact plan)", flush=True)
+hf = _hip.RasterHandle(d8, nrow, ncol, device=0, memspace=_hip.PFD_DEVICE)
+sync(); t0 = time.perf_counter()
+hf.fillnodata(fnd, _hip.PFD_F32, nodata_f=-9999.0, direction=_hip.PFD_UP, out=out4, memspace=_hip.PFD_DEVICE)
+sync(); t1 = time.perf_counter()
+hf.close(); del hf
+print(f"{'first fillnodata up':22s} {1e3*(t1-t0):10.2f} ms  (fresh handle: builds the exact plan)", flush=True)
+timed("fillnodata f32 up", lambda: h.fillnodata(fnd, _hip.PFD_F32, nodata_f=-9999.0, direction=_hip.PFD_UP, out=out4,
+                                               memspace=_hip.PFD_DEVICE))
+timed("fillnodata f32 dn max", lambda: h.fillnodata(fnd, _hip.PFD_F32, nodata_f=-9999.0, direction=_hip.PFD_DOWN,
+                                                   how=_hip.PFD_FILL_MAX, out=out4, memspace=_hip.PFD_DEVICE))
+timed("fillnodata f32 dn sum", lambda: h.fillnodata(fnd, _hip.PFD_F32, nodata_f=-9999.0, direction=_hip.PFD_DOWN,
+                                                   how=_hip.PFD_FILL_SUM, out=out4, memspace=_hip.PFD_DEVICE))
+fnd.free(); del fnd
 wi = _hip.DeviceBuffer(n * 4)
 wi.upload(np.random.default_rng(0).integers(0, 20, n, dtype=np.int32)) if n <= 200_000_000 else None
 if n <= 200_000_000:
