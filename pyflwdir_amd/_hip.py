@@ -528,21 +528,28 @@ class RasterHandle:
                                    memspace, ptr(brows), C.byref(unk)))
         return out, brows, int(unk.value)
 
+    def _block_sweep(self, halo_seed, dtype, call, code=None):
+        """The frame of the pfd_*_block sweeps: ``halo_seed`` is 2 * ncol host values (``dtype``: None keeps the array's;
+        ``code``: the payload code they must have) or a DeviceBuffer (pfd_set_block_io(PFD_DEVICE): the boundary rows stay
+        on the device); ``call(seed, brows, bad)`` makes the C call.  Returns (boundary rows [2, ncol] or None, own cells
+        failing their local equation — verify only)."""
+        brows = None
+        if not isinstance(halo_seed, DeviceBuffer):
+            halo_seed = np.ascontiguousarray(halo_seed, dtype=dtype)
+            assert halo_seed.size == 2 * self.ncol and (code is None or _PAYLOAD_CODE[halo_seed.dtype] == code)
+            brows = np.empty((2, self.ncol), halo_seed.dtype)
+        bad = C.c_int64(0)
+        check(call(ptr(halo_seed), ptr(brows), C.byref(bad)))
+        return brows, int(bad.value)
+
     def accuflux_block(self, data, dtype_code, halo_seed, out, nodata_i=0, nodata_f=0.0, has_nodata=0, by_row=False,
                        verify=False, memspace=PFD_HOST, direction=PFD_UP):
         """accuflux (either direction) of a row block whose halo cells hold ``halo_seed`` (2 * ncol values of the result
         type, host); data and ``out`` cover the block's device raster (own + halo rows), ``by_row``: one host value per
         device row.  Returns (boundary rows [2, ncol], own cells failing their local equation — verify only)."""
-        brows = None
-        if not isinstance(halo_seed, DeviceBuffer):
-            halo_seed = np.ascontiguousarray(halo_seed)
-            assert halo_seed.size == 2 * self.ncol and _PAYLOAD_CODE[halo_seed.dtype] == dtype_code
-            brows = np.empty((2, self.ncol), halo_seed.dtype)
-        bad = C.c_int64(0)
-        check(lib().pfd_accuflux_block(self._h, dtype_code, ptr(data), 1 if by_row else 0, int(nodata_i), float(nodata_f),
-                                       int(has_nodata), int(direction), ptr(halo_seed), 1 if verify else 0, ptr(out),
-                                       memspace, ptr(brows), C.byref(bad)))
-        return brows, int(bad.value)
+        return self._block_sweep(halo_seed, None, lambda seed, brows, bad: lib().pfd_accuflux_block(
+            self._h, dtype_code, ptr(data), 1 if by_row else 0, int(nodata_i), float(nodata_f), int(has_nodata),
+            int(direction), seed, 1 if verify else 0, ptr(out), memspace, brows, bad), code=dtype_code)
 
     def fillnodata(self, data, dtype_code, nodata_i=0, nodata_f=0.0, has_nodata=1, direction=PFD_DOWN, how=PFD_FILL_MAX,
                    out=None, memspace=PFD_HOST):
@@ -557,34 +564,20 @@ class RasterHandle:
                          direction=PFD_DOWN, how=PFD_FILL_MAX, verify=False, memspace=PFD_HOST):
         """fillnodata of a row block whose halo cells hold ``halo_seed`` (2 * ncol values of the lane type, host); data
         and ``out`` cover the block's device raster.  Returns (boundary rows [2, ncol], failing own cells — verify only)."""
-        brows = None
-        if not isinstance(halo_seed, DeviceBuffer):
-            halo_seed = np.ascontiguousarray(halo_seed)
-            assert halo_seed.size == 2 * self.ncol
-            brows = np.empty((2, self.ncol), halo_seed.dtype)
-        bad = C.c_int64(0)
-        check(lib().pfd_fillnodata_block(self._h, dtype_code, ptr(data), int(nodata_i), float(nodata_f), int(has_nodata),
-                                         int(direction), int(how), ptr(halo_seed), 1 if verify else 0, ptr(out), memspace,
-                                         ptr(brows), C.byref(bad)))
-        return brows, int(bad.value)
+        return self._block_sweep(halo_seed, None, lambda seed, brows, bad: lib().pfd_fillnodata_block(
+            self._h, dtype_code, ptr(data), int(nodata_i), float(nodata_f), int(has_nodata), int(direction), int(how), seed,
+            1 if verify else 0, ptr(out), memspace, brows, bad))
 
     def stream_distance_block(self, mask, step_lengths, halo_seed, out, verify=False, memspace=PFD_HOST):
         """stream_distance of a row block whose halo cells hold ``halo_seed`` (2 * ncol int32, or float32 with
         ``step_lengths``: the table rows of the block's device raster).  Returns (boundary rows, failing own cells)."""
         real = step_lengths is not None
-        dt = np.float32 if real else np.int32
-        dev_seed = isinstance(halo_seed, DeviceBuffer)
-        if not dev_seed:
-            halo_seed = np.ascontiguousarray(halo_seed, dtype=dt)
-            assert halo_seed.size == 2 * self.ncol
         if real:
             step_lengths = np.ascontiguousarray(step_lengths, dtype=np.float32)
             assert step_lengths.size == 3 * (2 * (self.nrow + sum(self.halo)) - 1)
-        brows = None if dev_seed else np.empty((2, self.ncol), dt)
-        bad = C.c_int64(0)
-        check(lib().pfd_stream_distance_block(self._h, ptr(mask), int(real), ptr(step_lengths), ptr(halo_seed),
-                                              1 if verify else 0, ptr(out), memspace, ptr(brows), C.byref(bad)))
-        return brows, int(bad.value)
+        return self._block_sweep(halo_seed, np.float32 if real else np.int32, lambda seed, brows, bad:
+                                 lib().pfd_stream_distance_block(self._h, ptr(mask), int(real), ptr(step_lengths), seed,
+                                                                 1 if verify else 0, ptr(out), memspace, brows, bad))
 
     def trib_info_block(self, uparea, dtype_code, mask=None, upa_min=0.0, out=None, memspace=PFD_HOST):
         """One byte per cell of the block's device raster: slot of the main upstream cell | (more than one upstream cell
@@ -597,29 +590,16 @@ class RasterHandle:
     def stream_order_classic_block(self, tinfo, mask, halo_seed, out, verify=False, memspace=PFD_HOST):
         """Classic stream order of a row block whose halo cells hold ``halo_seed`` (2 * ncol uint8).  Returns (boundary
         rows [2, ncol], own cells failing their local equation — verify only)."""
-        brows = None
-        if not isinstance(halo_seed, DeviceBuffer):
-            halo_seed = np.ascontiguousarray(halo_seed, dtype=np.uint8)
-            assert halo_seed.size == 2 * self.ncol
-            brows = np.empty((2, self.ncol), np.uint8)
-        bad = C.c_int64(0)
-        check(lib().pfd_stream_order_classic_block(self._h, ptr(tinfo), ptr(mask), ptr(halo_seed), 1 if verify else 0, ptr(out),
-                                                   memspace, ptr(brows), C.byref(bad)))
-        return brows, int(bad.value)
+        return self._block_sweep(halo_seed, np.uint8, lambda seed, brows, bad: lib().pfd_stream_order_classic_block(
+            self._h, ptr(tinfo), ptr(mask), seed, 1 if verify else 0, ptr(out), memspace, brows, bad))
 
     def floodplains_block(self, elevtn, elev_code, is_stream, stream_h, halo_seed, state, verify=False, memspace=PFD_HOST):
         """dem.floodplains of a row block whose halo cells hold the floodplain state ``halo_seed`` (2 * ncol records of
         FLOOD_STATE, host, or a DeviceBuffer after set_block_io); ``state`` covers the block's device raster.  Returns
         (boundary rows [2, ncol] of FLOOD_STATE, own cells failing their local equation — verify only)."""
-        brows = None
-        if not isinstance(halo_seed, DeviceBuffer):
-            halo_seed = np.ascontiguousarray(halo_seed, dtype=FLOOD_STATE)
-            assert halo_seed.size == 2 * self.ncol
-            brows = np.empty((2, self.ncol), FLOOD_STATE)
-        bad = C.c_int64(0)
-        check(lib().pfd_floodplains_block(self._h, int(elev_code), ptr(elevtn), ptr(is_stream), ptr(stream_h), ptr(halo_seed),
-                                          1 if verify else 0, ptr(state), memspace, ptr(brows), C.byref(bad)))
-        return brows, int(bad.value)
+        return self._block_sweep(halo_seed, FLOOD_STATE, lambda seed, brows, bad: lib().pfd_floodplains_block(
+            self._h, int(elev_code), ptr(elevtn), ptr(is_stream), ptr(stream_h), seed, 1 if verify else 0, ptr(state),
+            memspace, brows, bad))
 
     def floodplains_block_flags(self, state: "DeviceBuffer", out=None) -> np.ndarray:
         """int8 flags of the block's own rows from its device-resident floodplain state (pfd_floodplains_block_flags);
@@ -633,15 +613,8 @@ class RasterHandle:
     def strahler_block(self, mask, halo_seed, out, verify=False, memspace=PFD_HOST):
         """Strahler order of a row block whose halo cells hold ``halo_seed`` (2 * ncol uint8, host).  Returns
         (boundary rows [2, ncol], own cells failing their local equation — verify only)."""
-        brows = None
-        if not isinstance(halo_seed, DeviceBuffer):
-            halo_seed = np.ascontiguousarray(halo_seed, dtype=np.uint8)
-            assert halo_seed.size == 2 * self.ncol
-            brows = np.empty((2, self.ncol), np.uint8)
-        bad = C.c_int64(0)
-        check(lib().pfd_strahler_block(self._h, ptr(mask), ptr(halo_seed), 1 if verify else 0, ptr(out), memspace,
-                                       ptr(brows), C.byref(bad)))
-        return brows, int(bad.value)
+        return self._block_sweep(halo_seed, np.uint8, lambda seed, brows, bad: lib().pfd_strahler_block(
+            self._h, ptr(mask), seed, 1 if verify else 0, ptr(out), memspace, brows, bad))
 
     def verify_basins(self, outlets, ids, labels, memspace=PFD_HOST) -> dict:
         """Local-equation check of a basins() result with uint32 ids (see include/pfd.h)."""

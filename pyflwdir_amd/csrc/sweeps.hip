@@ -1649,6 +1649,17 @@ static int hand_block_update(pfd_raster *h, HandBlockState *st, const u8 *drain,
   return hand_block_collect(h, st, out, true);  // drop what is known now
 }
 
+// first and last OWN row of a row block's result: what the neighbouring blocks need as their halo values
+template <class T>
+static int download_boundary_rows(pfd_raster *h, const T *out_dev, T *brows_host) {
+  if (!brows_host) return PFD_OK;
+  const size_t ncol = (size_t)h->ncol, own0 = (size_t)h->halo_top * ncol, own1 = own0 + (size_t)h->own_rows * ncol;
+  HIPCHK(hipMemcpyAsync(brows_host, out_dev + own0, ncol * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(brows_host + ncol, out_dev + own1 - ncol, ncol * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return PFD_OK;
+}
+
 extern "C" int pfd_hand_block(pfd_raster *h, const uint8_t *drain, int elev_dtype, const void *elevtn,
                               const double *halo_seed_host, int update, double *out, int memspace,
                               double *boundary_rows_host, int64_t *n_unknown) {
@@ -1743,14 +1754,8 @@ extern "C" int pfd_hand_block(pfd_raster *h, const uint8_t *drain, int elev_dtyp
       st->unknown = 0, st->m = 0, st->valid = true;
     }
   }
-  const size_t ncol = (size_t)h->ncol, own0 = (size_t)h->halo_top * ncol, own1 = own0 + (size_t)h->own_rows * ncol;
   if (n_unknown) *n_unknown = (int64_t)st->unknown;  // (the listed cells are own cells: halo cells are never listed)
-  if (boundary_rows_host) {  // first and last OWN row: what the neighbouring blocks need as their halo heights
-    HIPCHK(hipMemcpyAsync(boundary_rows_host, (const double *)o.dev + own0, ncol * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(boundary_rows_host + ncol, (const double *)o.dev + own1 - ncol, ncol * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
+  PFDCHK(download_boundary_rows(h, (const double *)o.dev, boundary_rows_host));
   return o.finish(h->stream);
 }
 
@@ -1801,16 +1806,58 @@ __global__ void __launch_bounds__(256) k_verify_up(Op op, const u8 *__restrict__
   const u64 m = __ballot(b);
   if (m && (threadIdx.x & 63u) == 0u) atomicAdd(bad, (unsigned long long)__popcll(m));
 }
-template <class Op, class T>
-static int up_block_run(pfd_raster *h, const Op &op0, T *out_dev, const T *seed_dev, int verify, T *brows_host,
-                        int64_t *n_bad, const char *name) {
+// The frame of a pfd_*_block call: the halo seeds (2 * ncol values of `elem` bytes, in h->block_seed_space) and the
+// result `out` (n values).  A verify of a host `out` checks the caller's values: they travel to the device first.
+struct BlockFrame {
+  pfd_raster *h;
+  int verify;
+  void *brows_host;  // first and last own row of the result, for the neighbouring blocks (NULL: not wanted)
+  int64_t *n_bad;    // verify: the own cells failing their local equation
+  InArg sd;
+  OutArg o;
+  int bind(const void *seed_host, void *out, size_t elem, int memspace) {
+    PFDCHK(sd.bind(seed_host, 2 * (size_t)h->ncol * elem, h->block_seed_space, h->stream));
+    PFDCHK(o.bind(out, (size_t)h->n * elem, memspace));
+    if (verify && memspace == PFD_HOST) HIPCHK(hipMemcpyAsync(o.dev, out, (size_t)h->n * elem, hipMemcpyHostToDevice, h->stream));
+    return PFD_OK;
+  }
+  template <class T>
+  T *out() const { return (T *)o.dev; }
+  int finish() { return verify ? PFD_OK : o.finish(h->stream); }
+};
+// the halo rows of the result take their seeds (the neighbours' boundary rows)
+template <class T>
+static int seed_halo_rows(pfd_raster *h, T *out_dev, const T *seed_dev) {
   const size_t ncol = (size_t)h->ncol, own0 = (size_t)h->halo_top * ncol, nown = (size_t)h->own_rows * ncol;
   if (h->halo_top)
     HIPCHK(hipMemcpyAsync(out_dev + own0 - ncol, seed_dev, ncol * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
   if (h->halo_bot)
     HIPCHK(hipMemcpyAsync(out_dev + own0 + nown, seed_dev + ncol, ncol * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+  return PFD_OK;
+}
+// the count of a verify kernel, `launch(counter)`, in *n_bad
+template <class Launch>
+static int count_bad_cells(pfd_raster *h, const char *seg, int64_t *n_bad, Launch launch) {
+  pfd_seg_begin(h, seg);
+  HIPCHK(hipMemsetAsync(h->ctrl, 0, sizeof(u64), h->stream));
+  launch((unsigned long long *)h->ctrl);
+  KCHK();
+  pfd_seg_end(h, 1);
+  u64 bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, h->ctrl, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (n_bad) *n_bad = (int64_t)bad;
+  return PFD_OK;
+}
+template <class T, class Op>
+static int up_block_run(const Op &op0, BlockFrame &f, const char *name) {
+  pfd_raster *h = f.h;
+  T *out_dev = f.out<T>();
+  const T *seed_dev = (const T *)f.sd.dev;
+  const size_t own0 = (size_t)h->halo_top * h->ncol, nown = (size_t)h->own_rows * h->ncol;
+  PFDCHK(seed_halo_rows(h, out_dev, seed_dev));
   OwnRows<Op> op{op0, (u32)own0, (u32)nown};
-  if (verify) {
+  if (f.verify) {
     const u8 *kids = nullptr;  // per cell: the neighbours draining into it, halo cells included
     if (h->xplan_state == 1) {
       kids = ((ExactPlan *)h->xplan)->kids;
@@ -1818,16 +1865,10 @@ static int up_block_run(pfd_raster *h, const Op &op0, T *out_dev, const T *seed_
       PFDCHK(pfd_ensure_seq_aux(h));
       kids = h->cell_kids;
     }
-    pfd_seg_begin(h, "verify_up_block");
-    HIPCHK(hipMemsetAsync(h->ctrl, 0, sizeof(u64), h->stream));
-    k_verify_up<OwnRows<Op>, T><<<cdiv_u32((u64)nown, 256), 256, 0, h->stream>>>(op, h->ncode, kids, out_dev, (u32)own0,
-                                                                                (u32)nown, (unsigned long long *)h->ctrl);
-    KCHK();
-    pfd_seg_end(h, 1);
-    u64 bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, h->ctrl, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (n_bad) *n_bad = (int64_t)bad;
+    PFDCHK(count_bad_cells(h, "verify_up_block", f.n_bad, [&](unsigned long long *bad) {
+      k_verify_up<OwnRows<Op>, T><<<cdiv_u32((u64)nown, 256), 256, 0, h->stream>>>(op, h->ncode, kids, out_dev, (u32)own0,
+                                                                                  (u32)nown, bad);
+    }));
   } else if (h->xplan_state == 1) {
     // exact-order engine: the tile pass writes every cell, the halo cells among them; their given values go back in
     // before the trunk rounds read them (run_exact_up)
@@ -1838,14 +1879,10 @@ static int up_block_run(pfd_raster *h, const Op &op0, T *out_dev, const T *seed_
   } else {
     PFDCHK(run_up(h, op, name));
   }
-  if (brows_host) {  // first and last OWN row: the neighbouring blocks' halo values
-    HIPCHK(hipMemcpyAsync(brows_host, out_dev + own0, ncol * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(brows_host + ncol, out_dev + own0 + nown - ncol, ncol * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return PFD_OK;
+  return download_boundary_rows(h, out_dev, (T *)f.brows_host);
 }
-static int up_block_prepare(pfd_raster *h, const char *what) {
+// the checks every row-block entry point starts with, and the structure the block sweeps on (up- and down-sweeps)
+static int block_prepare(pfd_raster *h, const char *what) {
   PFDCHK(pfd_check_handle(h));
   PFDCHK(pfd_reject_general(h, what));
   if (!(h->halo_top || h->halo_bot) && h->own_rows != h->nrow) {
@@ -1889,42 +1926,26 @@ __global__ void __launch_bounds__(256) k_verify_down(Op op, const u8 *__restrict
   const u64 m = __ballot(b);
   if (m && (threadIdx.x & 63u) == 0u) atomicAdd(bad, (unsigned long long)__popcll(m));
 }
-template <class Op, class T>
-static int down_block_run(pfd_raster *h, const Op &op0, T *out_dev, const T *seed_dev, int verify, T *brows_host,
-                          int64_t *n_bad, const char *name) {
-  const size_t ncol = (size_t)h->ncol, own0 = (size_t)h->halo_top * ncol, nown = (size_t)h->own_rows * ncol;
-  auto seed_rows = [&]() -> int {
-    if (h->halo_top)
-      HIPCHK(hipMemcpyAsync(out_dev + own0 - ncol, seed_dev, ncol * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
-    if (h->halo_bot)
-      HIPCHK(hipMemcpyAsync(out_dev + own0 + nown, seed_dev + ncol, ncol * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
-    return PFD_OK;
-  };
-  PFDCHK(seed_rows());
-  if (verify) {
-    pfd_seg_begin(h, "verify_down_block");
-    HIPCHK(hipMemsetAsync(h->ctrl, 0, sizeof(u64), h->stream));
-    k_verify_down<Op, T><<<cdiv_u32((u64)nown, 256), 256, 0, h->stream>>>(op0, h->ncode, h->geo, out_dev, (u32)own0, (u32)nown,
-                                                                        (unsigned long long *)h->ctrl);
-    KCHK();
-    pfd_seg_end(h, 1);
-    u64 bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, h->ctrl, sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (n_bad) *n_bad = (int64_t)bad;
+template <class T, class Op>
+static int down_block_run(const Op &op0, BlockFrame &f, const char *name) {
+  pfd_raster *h = f.h;
+  T *out_dev = f.out<T>();
+  const T *seed_dev = (const T *)f.sd.dev;
+  const size_t own0 = (size_t)h->halo_top * h->ncol, nown = (size_t)h->own_rows * h->ncol;
+  PFDCHK(seed_halo_rows(h, out_dev, seed_dev));
+  if (f.verify) {
+    PFDCHK(count_bad_cells(h, "verify_down_block", f.n_bad, [&](unsigned long long *bad) {
+      k_verify_down<Op, T><<<cdiv_u32((u64)nown, 256), 256, 0, h->stream>>>(op0, h->ncode, h->geo, out_dev, (u32)own0, (u32)nown,
+                                                                          bad);
+    }));
   } else if (h->xplan_state == 1) {
     PFDCHK(run_exact_down(h, op0, "exact_down_block"));  // (halo cells: given values, loaded and written back unchanged)
   } else {
     HaloSeeded<Op, T> op{op0, seed_dev, (u32)(h->halo_top + h->own_rows - 1)};
     PFDCHK(run_down(h, op, name));
-    PFDCHK(seed_rows());  // (the level engine stored the seeds of the VALID halo cells only)
+    PFDCHK(seed_halo_rows(h, out_dev, seed_dev));  // (the level engine stored the seeds of the VALID halo cells only)
   }
-  if (brows_host) {
-    HIPCHK(hipMemcpyAsync(brows_host, out_dev + own0, ncol * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(brows_host + ncol, out_dev + own0 + nown - ncol, ncol * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return PFD_OK;
+  return download_boundary_rows(h, out_dev, (T *)f.brows_host);
 }
 
 // pfd_set_block_update modes 1 / 2 keep POINTERS into the result buffer between calls: with a host `out` that buffer is
@@ -1941,49 +1962,44 @@ template <class T>
 static int accuflux_block_t(pfd_raster *h, const void *data, bool by_row, T nodata, int has_nodata, int direction,
                             const void *seed_host, int verify, void *out, int memspace, void *brows_host, int64_t *n_bad) {
   if (!verify) PFDCHK(block_update_needs_device(h, memspace, "pfd_accuflux_block"));
-  InArg d, sd;
+  InArg d;
   if (by_row)
     PFDCHK(d.bind(data, (size_t)h->nrow * sizeof(T), PFD_HOST, h->stream));
   else
     PFDCHK(d.bind(data, (size_t)h->n * sizeof(T), memspace, h->stream));
-  PFDCHK(sd.bind(seed_host, 2 * (size_t)h->ncol * sizeof(T), h->block_seed_space, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * sizeof(T), memspace));
-  if (verify && memspace == PFD_HOST)
-    HIPCHK(hipMemcpyAsync(o.dev, out, (size_t)h->n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+  BlockFrame f{h, verify, brows_host, n_bad};
+  PFDCHK(f.bind(seed_host, out, sizeof(T), memspace));
+  T *o = f.out<T>();
   // (an update — pfd_set_block_update(h, 2) after a kept sweep of the same operation into the same buffer — starts
   //  from the result in `out`)
-  const bool upd = direction == PFD_UP && xinc_applies(h, o.dev, by_row ? typeid(AccuUp<T, RowData<T>>).hash_code()
-                                                                        : typeid(AccuUp<T>).hash_code());
+  const bool upd = direction == PFD_UP && xinc_applies(h, o, by_row ? typeid(AccuUp<T, RowData<T>>).hash_code()
+                                                                    : typeid(AccuUp<T>).hash_code());
   if (!verify && !upd) {
     pfd_seg_begin(h, "init");
     if (by_row) {
-      k_fill_rows<T><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>((const T *)d.dev, h->geo, (T *)o.dev);
+      k_fill_rows<T><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>((const T *)d.dev, h->geo, o);
       KCHK();
     } else {
-      HIPCHK(hipMemcpyAsync(o.dev, d.dev, (size_t)h->n * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(o, d.dev, (size_t)h->n * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
     }
     pfd_seg_end(h, 1);
   }
-  if (direction == PFD_DOWN && by_row) {
-    AccuDown<T, RowData<T>> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
-    PFDCHK(down_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)brows_host, n_bad, "sweep_accuflux_down_block"));
-  } else if (direction == PFD_DOWN) {
-    AccuDown<T> op{h->ncode, h->geo, CellData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
-    PFDCHK(down_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)brows_host, n_bad, "sweep_accuflux_down_block"));
-  } else if (by_row) {
-    AccuUp<T, RowData<T>> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
-    PFDCHK(up_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)brows_host, n_bad, "sweep_accuflux_block"));
-  } else {
-    AccuUp<T> op{h->ncode, h->geo, CellData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
-    PFDCHK(up_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)brows_host, n_bad, "sweep_accuflux_block"));
-  }
-  return verify ? PFD_OK : o.finish(h->stream);
+  auto sweep = [&](auto data) -> int {  // (RowData: one value per device row, CellData: one per cell)
+    typedef decltype(data) D;
+    if (direction == PFD_DOWN) {
+      AccuDown<T, D> op{h->ncode, h->geo, data, o, nodata, has_nodata};
+      return down_block_run<T>(op, f, "sweep_accuflux_down_block");
+    }
+    AccuUp<T, D> op{h->ncode, h->geo, data, o, nodata, has_nodata};
+    return up_block_run<T>(op, f, "sweep_accuflux_block");
+  };
+  PFDCHK(by_row ? sweep(RowData<T>{(const T *)d.dev, h->geo}) : sweep(CellData<T>{(const T *)d.dev, h->geo}));
+  return f.finish();
 }
 extern "C" int pfd_accuflux_block(pfd_raster *h, int dtype, const void *data, int by_row, int64_t nodata_i, double nodata_f,
                                   int has_nodata, int direction, const void *halo_seed_host, int verify, void *out,
                                   int memspace, void *boundary_rows_host, int64_t *n_bad) {
-  PFDCHK(up_block_prepare(h, "pfd_accuflux_block"));
+  PFDCHK(block_prepare(h, "pfd_accuflux_block"));
   if (!data || !out || !halo_seed_host || (direction != PFD_UP && direction != PFD_DOWN)) {
     pfd_set_error("pfd_accuflux_block: bad arguments");
     return PFD_EINVAL;
@@ -2005,7 +2021,7 @@ extern "C" int pfd_accuflux_block(pfd_raster *h, int dtype, const void *data, in
 extern "C" int pfd_fillnodata_block(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f,
                                     int has_nodata, int direction, int how, const void *halo_seed_host, int verify,
                                     void *out, int memspace, void *boundary_rows_host, int64_t *n_bad) {
-  PFDCHK(up_block_prepare(h, "pfd_fillnodata_block"));
+  PFDCHK(block_prepare(h, "pfd_fillnodata_block"));
   PFDCHK(fill_check_args(data, out, direction, how, "pfd_fillnodata_block"));
   if (!halo_seed_host) {
     pfd_set_error("pfd_fillnodata_block: bad arguments");
@@ -2020,56 +2036,49 @@ extern "C" int pfd_fillnodata_block(pfd_raster *h, int dtype, const void *data, 
     pfd_set_error("pfd_fillnodata_block: pfd_set_block_update does not apply");
     return PFD_EINVAL;
   }
-  InArg d, sd;
+  InArg d;
   PFDCHK(d.bind(data, (size_t)h->n * lane, memspace, h->stream));
-  PFDCHK(sd.bind(halo_seed_host, 2 * (size_t)h->ncol * lane, h->block_seed_space, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * lane, memspace));
-  if (verify && memspace == PFD_HOST)
-    HIPCHK(hipMemcpyAsync(o.dev, out, (size_t)h->n * lane, hipMemcpyHostToDevice, h->stream));
+  BlockFrame f{h, verify, boundary_rows_host, n_bad};
+  PFDCHK(f.bind(halo_seed_host, out, lane, memspace));
   if (!verify) {
     pfd_seg_begin(h, "init");
-    HIPCHK(hipMemcpyAsync(o.dev, d.dev, (size_t)h->n * lane, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(f.o.dev, d.dev, (size_t)h->n * lane, hipMemcpyDeviceToDevice, h->stream));
     pfd_seg_end(h, 1);
   }
   auto fdown = [&](auto r) -> int {
     typedef decltype(r.nodata) T;
-    FillDown<T> op{h->ncode, h->geo, (const T *)d.dev, (T *)o.dev, r, h->halo_raw};
-    return up_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)boundary_rows_host, n_bad,
-                        "sweep_fillnodata_down_block");
+    FillDown<T> op{h->ncode, h->geo, (const T *)d.dev, f.out<T>(), r, h->halo_raw};
+    return up_block_run<T>(op, f, "sweep_fillnodata_down_block");
   };
   auto fup = [&](auto r) -> int {
     typedef decltype(r.nodata) T;
-    FillUp<T> op{h->ncode, h->geo, (const T *)d.dev, (T *)o.dev, r};
-    return down_block_run(h, op, (T *)o.dev, (const T *)sd.dev, verify, (T *)boundary_rows_host, n_bad,
-                          "sweep_fillnodata_up_block");
+    FillUp<T> op{h->ncode, h->geo, (const T *)d.dev, f.out<T>(), r};
+    return down_block_run<T>(op, f, "sweep_fillnodata_up_block");
   };
   PFDCHK(fill_dispatch(dtype, direction == PFD_DOWN, nodata_i, nodata_f, has_nodata, how, "pfd_fillnodata_block", fdown,
                        fup));
-  return verify ? PFD_OK : o.finish(h->stream);
+  return f.finish();
 }
 extern "C" int pfd_strahler_block(pfd_raster *h, const uint8_t *mask, const uint8_t *halo_seed_host, int verify, uint8_t *out,
                                   int memspace, uint8_t *boundary_rows_host, int64_t *n_bad) {
-  PFDCHK(up_block_prepare(h, "pfd_strahler_block"));
+  PFDCHK(block_prepare(h, "pfd_strahler_block"));
   if (!out || !halo_seed_host) {
     pfd_set_error("pfd_strahler_block: bad arguments");
     return PFD_EINVAL;
   }
   if (!verify) PFDCHK(block_update_needs_device(h, memspace, "pfd_strahler_block"));
-  InArg m, sd;
+  InArg m;
   PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
-  PFDCHK(sd.bind(halo_seed_host, 2 * (size_t)h->ncol, h->block_seed_space, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n, memspace));
-  if (verify && memspace == PFD_HOST) HIPCHK(hipMemcpyAsync(o.dev, out, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
-  if (!verify && !xinc_applies(h, o.dev, typeid(Strahler).hash_code())) {
+  BlockFrame f{h, verify, boundary_rows_host, n_bad};
+  PFDCHK(f.bind(halo_seed_host, out, 1, memspace));
+  if (!verify && !xinc_applies(h, f.o.dev, typeid(Strahler).hash_code())) {
     pfd_seg_begin(h, "init");
-    HIPCHK(hipMemsetAsync(o.dev, 0, (size_t)h->n, h->stream));
+    HIPCHK(hipMemsetAsync(f.o.dev, 0, (size_t)h->n, h->stream));
     pfd_seg_end(h, 1);
   }
-  Strahler op{h->ncode, h->geo, (const u8 *)m.dev, (u8 *)o.dev};
-  PFDCHK(up_block_run(h, op, (u8 *)o.dev, (const u8 *)sd.dev, verify, boundary_rows_host, n_bad, "sweep_strahler_block"));
-  return verify ? PFD_OK : o.finish(h->stream);
+  Strahler op{h->ncode, h->geo, (const u8 *)m.dev, f.out<u8>()};
+  PFDCHK(up_block_run<u8>(op, f, "sweep_strahler_block"));
+  return f.finish();
 }
 
 extern "C" int pfd_hand(pfd_raster *h, const uint8_t *drain, int elev_dtype, const void *elevtn, double *out,
@@ -2456,13 +2465,12 @@ __global__ void __launch_bounds__(256) k_trib_flag_info(const u8 *__restrict__ n
 }
 extern "C" int pfd_trib_info_block(pfd_raster *h, int dtype, const void *uparea, double upa_min, const uint8_t *mask,
                                    uint8_t *tinfo, int memspace) {
-  PFDCHK(up_block_prepare(h, "pfd_trib_info_block"));
+  PFDCHK(block_prepare(h, "pfd_trib_info_block"));
   const size_t ps = payload_bytes(dtype);
   if (!uparea || !tinfo || !ps) {
     pfd_set_error("pfd_trib_info_block: bad arguments (dtype %d)", dtype);
     return PFD_EINVAL;
   }
-  PFDCHK(ensure_sweep_structure(h, true));
   const u8 *kids = nullptr;  // per cell: the neighbours draining into it, halo cells included
   if (h->xplan_state == 1) {
     kids = ((ExactPlan *)h->xplan)->kids;
@@ -2490,33 +2498,27 @@ extern "C" int pfd_trib_info_block(pfd_raster *h, int dtype, const void *uparea,
 extern "C" int pfd_stream_order_classic_block(pfd_raster *h, const uint8_t *tinfo, const uint8_t *mask,
                                               const uint8_t *halo_seed_host, int verify, uint8_t *out, int memspace,
                                               uint8_t *boundary_rows_host, int64_t *n_bad) {
-  PFDCHK(up_block_prepare(h, "pfd_stream_order_classic_block"));
+  PFDCHK(block_prepare(h, "pfd_stream_order_classic_block"));
   if (!tinfo || !out || !halo_seed_host) {
     pfd_set_error("pfd_stream_order_classic_block: bad arguments");
     return PFD_EINVAL;
   }
-  PFDCHK(ensure_sweep_structure(h, true));
-  InArg ti, m, sd;
+  InArg ti, m;
   PFDCHK(ti.bind(tinfo, (size_t)h->n, memspace, h->stream));
   PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
-  PFDCHK(sd.bind(halo_seed_host, 2 * (size_t)h->ncol, h->block_seed_space, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n, memspace));
-  if (verify && memspace == PFD_HOST) HIPCHK(hipMemcpyAsync(o.dev, out, (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+  BlockFrame f{h, verify, boundary_rows_host, n_bad};
+  PFDCHK(f.bind(halo_seed_host, out, 1, memspace));
   DevBuf flag;
   PFDCHK(flag.alloc((size_t)h->n));
   pfd_seg_begin(h, "init");
-  if (!verify && h->xplan_state != 1) HIPCHK(hipMemsetAsync(o.dev, 0, (size_t)h->n, h->stream));
+  if (!verify && h->xplan_state != 1) HIPCHK(hipMemsetAsync(f.o.dev, 0, (size_t)h->n, h->stream));
   k_trib_flag_info<<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo, (const u8 *)ti.dev, flag.as<u8>());
   KCHK();
   pfd_seg_end(h, 2);
-  Classic op{h->ncode, h->geo, flag.as<u8>(), (const u8 *)m.dev, (u8 *)o.dev};
-  PFDCHK(down_block_run(h, op, (u8 *)o.dev, (const u8 *)sd.dev, verify, boundary_rows_host, n_bad, "sweep_classic_block"));
-  if (verify) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PFD_OK;
-  }
-  return o.finish(h->stream);  // (synchronises: `flag` may be released afterwards)
+  Classic op{h->ncode, h->geo, flag.as<u8>(), (const u8 *)m.dev, f.out<u8>()};
+  PFDCHK(down_block_run<u8>(op, f, "sweep_classic_block"));
+  if (verify) HIPCHK(hipStreamSynchronize(h->stream));  // (`flag` may be released afterwards: finish() synchronises otherwise)
+  return f.finish();
 }
 
 extern "C" int pfd_stream_distance(pfd_raster *h, const uint8_t *mask, int real_length, const float *step_lengths,
@@ -2560,37 +2562,33 @@ extern "C" int pfd_stream_distance(pfd_raster *h, const uint8_t *mask, int real_
 extern "C" int pfd_stream_distance_block(pfd_raster *h, const uint8_t *mask, int real_length, const float *step_lengths,
                                          const void *halo_seed_host, int verify, void *out, int memspace,
                                          void *boundary_rows_host, int64_t *n_bad) {
-  PFDCHK(up_block_prepare(h, "pfd_stream_distance_block"));
+  PFDCHK(block_prepare(h, "pfd_stream_distance_block"));
   if (!out || !halo_seed_host || (real_length && !step_lengths)) {
     pfd_set_error("pfd_stream_distance_block: bad arguments");
     return PFD_EINVAL;
   }
-  InArg m, tab, sd;
+  InArg m, tab;
   PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
   if (real_length) PFDCHK(tab.bind(step_lengths, 3 * (size_t)(2 * h->nrow - 1) * sizeof(float), PFD_HOST, h->stream));
-  PFDCHK(sd.bind(halo_seed_host, 2 * (size_t)h->ncol * 4, h->block_seed_space, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * 4, memspace));
-  if (verify && memspace == PFD_HOST) HIPCHK(hipMemcpyAsync(o.dev, out, (size_t)h->n * 4, hipMemcpyHostToDevice, h->stream));
+  BlockFrame f{h, verify, boundary_rows_host, n_bad};
+  PFDCHK(f.bind(halo_seed_host, out, 4, memspace));
   if (!verify && h->xplan_state != 1) {
     pfd_seg_begin(h, "init");
     if (real_length)
-      k_fill<float><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>((float *)o.dev, h->geo.n, -9999.0f);
+      k_fill<float><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(f.out<float>(), h->geo.n, -9999.0f);
     else
-      k_fill<i32><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>((i32 *)o.dev, h->geo.n, -9999);
+      k_fill<i32><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(f.out<i32>(), h->geo.n, -9999);
     KCHK();
     pfd_seg_end(h, 1);
   }
   if (real_length) {
-    Dist<float> op{h->ncode, h->geo, (const u8 *)m.dev, (const float *)tab.dev, (float *)o.dev};
-    PFDCHK(down_block_run(h, op, (float *)o.dev, (const float *)sd.dev, verify, (float *)boundary_rows_host, n_bad,
-                          "sweep_stream_distance_block"));
+    Dist<float> op{h->ncode, h->geo, (const u8 *)m.dev, (const float *)tab.dev, f.out<float>()};
+    PFDCHK(down_block_run<float>(op, f, "sweep_stream_distance_block"));
   } else {
-    Dist<i32> op{h->ncode, h->geo, (const u8 *)m.dev, nullptr, (i32 *)o.dev};
-    PFDCHK(down_block_run(h, op, (i32 *)o.dev, (const i32 *)sd.dev, verify, (i32 *)boundary_rows_host, n_bad,
-                          "sweep_stream_distance_block"));
+    Dist<i32> op{h->ncode, h->geo, (const u8 *)m.dev, nullptr, f.out<i32>()};
+    PFDCHK(down_block_run<i32>(op, f, "sweep_stream_distance_block"));
   }
-  return verify ? PFD_OK : o.finish(h->stream);
+  return f.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2664,35 +2662,29 @@ extern "C" int pfd_floodplains_block_flags(pfd_raster *h, const void *state_dev,
 extern "C" int pfd_floodplains_block(pfd_raster *h, int elev_dtype, const void *elevtn, const uint8_t *is_stream,
                                      const float *stream_h, const void *halo_seed_host, int verify, void *state,
                                      int memspace, void *boundary_rows_host, int64_t *n_bad) {
-  PFDCHK(up_block_prepare(h, "pfd_floodplains_block"));
+  PFDCHK(block_prepare(h, "pfd_floodplains_block"));
   if (!elevtn || !is_stream || !stream_h || !state || !halo_seed_host || (elev_dtype != PFD_F32 && elev_dtype != PFD_F64)) {
     pfd_set_error("pfd_floodplains_block: bad arguments (elevation dtype code %d)", elev_dtype);
     return PFD_EINVAL;
   }
-  PFDCHK(ensure_sweep_structure(h, true));
-  InArg el, sm, hh, sd;
+  InArg el, sm, hh;
   PFDCHK(el.bind(elevtn, (size_t)h->n * (elev_dtype == PFD_F32 ? 4 : 8), memspace, h->stream));
   PFDCHK(sm.bind(is_stream, (size_t)h->n, memspace, h->stream));
   PFDCHK(hh.bind(stream_h, (size_t)h->n * sizeof(float), memspace, h->stream));
-  PFDCHK(sd.bind(halo_seed_host, 2 * (size_t)h->ncol * sizeof(FloodV), h->block_seed_space, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(state, (size_t)h->n * sizeof(FloodV), memspace));
-  if (verify && memspace == PFD_HOST)
-    HIPCHK(hipMemcpyAsync(o.dev, state, (size_t)h->n * sizeof(FloodV), hipMemcpyHostToDevice, h->stream));
+  BlockFrame f{h, verify, boundary_rows_host, n_bad};
+  PFDCHK(f.bind(halo_seed_host, state, sizeof(FloodV), memspace));
   if (!verify) {
     pfd_seg_begin(h, "init");
-    k_flood_init<<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo.n, (FloodV *)o.dev);
+    k_flood_init<<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo.n, f.out<FloodV>());
     KCHK();
     pfd_seg_end(h, 1);
   }
   if (elev_dtype == PFD_F32) {
-    Flood<float> op{h->ncode, h->geo, (const u8 *)sm.dev, (const float *)hh.dev, (const float *)el.dev, (FloodV *)o.dev};
-    PFDCHK(down_block_run(h, op, (FloodV *)o.dev, (const FloodV *)sd.dev, verify, (FloodV *)boundary_rows_host, n_bad,
-                          "sweep_floodplains_block"));
+    Flood<float> op{h->ncode, h->geo, (const u8 *)sm.dev, (const float *)hh.dev, (const float *)el.dev, f.out<FloodV>()};
+    PFDCHK(down_block_run<FloodV>(op, f, "sweep_floodplains_block"));
   } else {
-    Flood<double> op{h->ncode, h->geo, (const u8 *)sm.dev, (const float *)hh.dev, (const double *)el.dev, (FloodV *)o.dev};
-    PFDCHK(down_block_run(h, op, (FloodV *)o.dev, (const FloodV *)sd.dev, verify, (FloodV *)boundary_rows_host, n_bad,
-                          "sweep_floodplains_block"));
+    Flood<double> op{h->ncode, h->geo, (const u8 *)sm.dev, (const float *)hh.dev, (const double *)el.dev, f.out<FloodV>()};
+    PFDCHK(down_block_run<FloodV>(op, f, "sweep_floodplains_block"));
   }
-  return verify ? PFD_OK : o.finish(h->stream);
+  return f.finish();
 }

@@ -102,9 +102,8 @@ def basins_blocks(d8: np.ndarray, nblocks: int, idxs, ids=None, devices=None) ->
     devices = devices or [0] * nblocks
     parts = _split_outlets(idxs, ids, nrow, ncol, nblocks)
     handles, outs, recs = [], [], []
-    for b, (r0, r1) in enumerate(block_rows(nrow, nblocks)):
-        a, e = block_slice(nrow, nblocks, b)
-        h = _hip.RasterHandle(d8[a:e], r1 - r0, ncol, device=devices[b], halo=halo_of(b, nblocks))
+    for b in range(nblocks):
+        h = _block_handle(d8, nblocks, b, devices)
         o, rec = _hip.basins_begin(h, parts[b][0], parts[b][1].astype(ids.dtype))
         handles.append(h), outs.append(o), recs.append(rec)
     allrec = np.stack(recs)
@@ -171,8 +170,7 @@ def hand_blocks(d8: np.ndarray, nblocks: int, drain, elevtn, devices=None, max_i
             if stream:
                 blocks.append(_StreamedHandBlock(d8[a:e], r1 - r0, ncol, devices[b], halo_of(b, nblocks), drain[a:e], elevtn[a:e], code))
                 continue
-            h = _hip.RasterHandle(d8[a:e], r1 - r0, ncol, device=devices[b], halo=halo_of(b, nblocks))
-            blocks.append(_HandBlock(h, drain[a:e], elevtn[a:e], code))
+            blocks.append(_HandBlock(_block_handle(d8, nblocks, b, devices), drain[a:e], elevtn[a:e], code))
         seeds = [np.full(2 * ncol, -np.inf) for _ in range(nblocks)]
         unknown_before, it = None, 0
         while True:
@@ -277,12 +275,12 @@ def _stream_blocks(cells: int, bytes_per_cell: int, devices) -> bool:
 
 
 class _StreamedBlock(_SeedGate):
-    """A row block that is on the device only while it sweeps (``make()`` builds it from the host arrays)."""
+    """A row block that is on the device only while it sweeps (``make()`` builds it from the host arrays): ``down`` is the
+    built block's, ``into`` its rows of the caller's result array, which the block fills after every sweep."""
 
-    def __init__(self, make):
-        self.make, self.host = make, None
+    def __init__(self, make, down, into):
+        self.make, self.down, self.into = make, down, into
         self.swept_with, self.brows = None, None
-        self.into = None  # (optional: the block's rows of the caller's result array — result(out=) of the block fills them)
 
     def _call(self, seed, verify):
         if verify:
@@ -290,10 +288,10 @@ class _StreamedBlock(_SeedGate):
                                       "(their state exceeds HBM_BUDGET)")
         blk = self.make()
         try:
-            if hasattr(blk, "incremental"):
-                blk.incremental = False  # (nothing is kept between the sweeps)
+            assert blk.down == self.down
+            blk.incremental = False  # (nothing is kept between the sweeps)
             out = blk._call(seed, False)
-            self.host = blk.result() if self.into is None else blk.result(self.into)
+            blk.result(self.into)
             return out
         finally:
             blk.close()
@@ -301,84 +299,96 @@ class _StreamedBlock(_SeedGate):
     def verify(self, seed):
         return self._call(seed, True)[1]
 
-    def result(self):
-        return self.host
-
     def close(self, close_handle=True):
         pass
-
-
-def _blocks_of(nblocks, make, relevant, stream):
-    """The blocks of a call: ``make(b)`` now, or a streamed stand-in; ``relevant(b)`` = its relevant_halo mask."""
-    import functools
-
-    blocks = []
-    try:
-        for b in range(nblocks):
-            blk = _StreamedBlock(functools.partial(make, b)) if stream else make(b)
-            blocks.append(blk)
-            blk.relevant = relevant(b)
-    except Exception:
-        for blk in blocks:
-            blk.close()
-        raise
-    return blocks
-
-
-def _result_array(blocks, rows, ncol, dtype):
-    """The whole result of a call, allocated up front: streamed blocks fill their rows when they sweep (``into``), resident
-    ones when ``_collect`` asks — no per-block host arrays, no concatenation (at 8.1 Gcells those were 32-65 GB allocated,
-    copied and freed again: seconds of page faults and munmap)."""
-    out = np.empty((rows[-1][1], ncol), dtype)
-    for b, blk in enumerate(blocks):
-        if isinstance(blk, _StreamedBlock):
-            blk.into = out[rows[b][0]:rows[b][1]]
-    return out
-
-
-def _collect(blocks, rows, out):
-    for b, blk in enumerate(blocks):
-        if not isinstance(blk, _StreamedBlock):
-            blk.result(out[rows[b][0]:rows[b][1]])
-    return out
 
 
 LAST_SWEEPS = []  # sweeps per block of the last fixpoint iteration of this process (diagnostics, tools/bench_down_blocks.py)
 
 
-class _UpBlock(_SeedGate):
-    """Device-resident state of one row block of an up-sweep (accuflux, Strahler) between the exchanges: payload and
-    result stay in HBM; only the two boundary rows travel."""
+class _Block(_SeedGate):
+    """Device-resident state of one row block between the exchanges: inputs and result stay in HBM; only the two boundary
+    rows travel.  A subclass uploads its inputs (``_upload``), sets up ``out`` and makes its pfd_*_block call in
+    ``_call(seed, verify)`` -> (boundary rows, own cells failing their local equation — verify only).  Every subclass
+    declares ``down``: whether its halo cells are the cells it drains INTO (a down-sweep, relevant_halo)."""
+
+    incremental = False  # pfd_set_block_update: the first sweep is kept, later ones fold only below changed halo seeds
+    sweeps = 0
+    owned = ()  # the device buffers close() frees (_own)
+
+    def __init__(self, handle, dtype):
+        self.h, self.dtype = handle, np.dtype(dtype)
+        self.nrows_dev = handle.nrow + sum(handle.halo)
+        self.swept_with, self.brows = None, None
+
+    def _own(self, buf):
+        self.owned = self.owned + (buf,)
+        return buf
+
+    def _upload(self, a):
+        a = np.ascontiguousarray(a)
+        return self._own(_hip.DeviceBuffer(a.nbytes, self.h.device).upload(a))
+
+    def _result_buffer(self, out=None):
+        """``out``: the caller's DEVICE buffer for the result over the block's device rows — stays resident, is not freed
+        here, and ``result()`` hands it back instead of a host copy."""
+        nbytes = self.nrows_dev * self.h.ncol * self.dtype.itemsize
+        self.out_given = out is not None
+        if self.out_given:
+            assert out.nbytes >= nbytes
+        self.out = out if self.out_given else self._own(_hip.DeviceBuffer(nbytes, self.h.device))
+
+    def sweep_dev(self, seed_buf):
+        """Sweep with the halo values in the DEVICE buffer ``seed_buf`` (the handle reads device seeds:
+        ``set_block_io(PFD_DEVICE)``); the boundary rows stay in ``self.out`` for the RCCL exchange."""
+        self._call(seed_buf, False)
+
+    def verify(self, seed):
+        """Own cells whose value is not the one their neighbours (halo values included) give."""
+        return self._call(seed, True)[1]
+
+    def result(self, out=None):
+        if self.out_given:
+            return self.out
+        ncol, sz = self.h.ncol, self.dtype.itemsize
+        return self.out.download(self.dtype, (self.h.nrow, ncol), offset_bytes=self.h.halo[0] * ncol * sz, out=out)
+
+    def close(self, close_handle=True):
+        for b in self.owned:
+            b.free()
+        if close_handle:
+            self.h.close()
+        elif self.incremental and self.sweeps:
+            self.h.set_block_update(0)  # (releases the kept sweep)
+
+
+class _UpBlock(_Block):
+    """One row block of accuflux (either direction), fillnodata, stream_distance (``kind`` "distance") or Strahler."""
 
     def __init__(self, handle, kind, dtype, payload=None, by_row=False, nodata=(0, 0.0, 0), mask=None, direction=_hip.PFD_UP,
                  out=None, code=None, how=_hip.PFD_FILL_MAX):
-        self.h, self.kind, self.dtype, self.by_row, self.nodata = handle, kind, np.dtype(dtype), by_row, nodata
-        self.direction = direction
+        super().__init__(handle, dtype)
+        self.kind, self.by_row, self.nodata, self.direction = kind, by_row, nodata, direction
         self.code, self.how = code, how  # (fillnodata: the payload code — narrow dtypes travel in int32 lanes — and merge rule)
-        ncol, dev = handle.ncol, handle.device
-        self.nrows_dev = handle.nrow + sum(handle.halo)
+        ncol = handle.ncol
         self.payload = self.mask = None
         if kind in ("accuflux", "fillnodata"):
             payload = np.ascontiguousarray(payload, dtype=self.dtype)
             assert payload.size == (self.nrows_dev if by_row else self.nrows_dev * ncol)
-            self.payload = payload if by_row else _hip.DeviceBuffer(payload.nbytes, dev).upload(payload)
+            self.payload = payload if by_row else self._upload(payload)
         elif mask is not None:
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
             assert mask.size == self.nrows_dev * ncol
-            self.mask = _hip.DeviceBuffer(mask.nbytes, dev).upload(mask)
+            self.mask = self._upload(mask)
         if kind == "distance":
             self.payload = None if payload is None else np.ascontiguousarray(payload, dtype=np.float32)  # step-length rows
-        # (``out``: the caller's DEVICE buffer for the result over the block's device rows — stays resident, is not freed here,
-        #  and ``result()`` hands it back instead of a host copy)
-        self.out_given = out is not None
-        if self.out_given:
-            assert out.nbytes >= self.nrows_dev * ncol * self.dtype.itemsize
-        self.out = out if self.out_given else _hip.DeviceBuffer(self.nrows_dev * ncol * self.dtype.itemsize, dev)
-        self.swept_with, self.brows = None, None
+        self._result_buffer(out)
+        # down-sweeps: accuflux "down", fillnodata "up" (a nodata cell takes its downstream value) and stream_distance
+        self.down = {"accuflux": direction == _hip.PFD_DOWN, "fillnodata": direction == _hip.PFD_UP,
+                     "distance": True}.get(kind, False)
         # accuflux "up" and Strahler: from the second sweep on only the chains below a changed halo seed are folded
         # again (pfd_set_block_update; the down-sweeps of accuflux "down" / stream_distance sweep the block each time)
         self.incremental = kind == "strahler" or (kind == "accuflux" and direction == _hip.PFD_UP)
-        self.sweeps = 0
 
     def _call(self, seed, verify):
         if self.incremental and not verify:
@@ -396,30 +406,6 @@ class _UpBlock(_SeedGate):
         if self.kind == "distance":
             return self.h.stream_distance_block(self.mask, self.payload, seed, self.out, verify=verify, memspace=_hip.PFD_DEVICE)
         return self.h.strahler_block(self.mask, seed, self.out, verify=verify, memspace=_hip.PFD_DEVICE)
-
-    def sweep_dev(self, seed_buf):
-        """Sweep with the halo values in the DEVICE buffer ``seed_buf`` (the handle reads device seeds:
-        ``set_block_io(PFD_DEVICE)``); the boundary rows stay in ``self.out`` for the RCCL exchange."""
-        self._call(seed_buf, False)
-
-    def verify(self, seed):
-        """Own cells whose value is not the one their upstream cells (halo values included) give."""
-        return self._call(seed, True)[1]
-
-    def result(self, out=None):
-        if self.out_given:
-            return self.out
-        ncol, sz = self.h.ncol, self.dtype.itemsize
-        return self.out.download(self.dtype, (self.h.nrow, ncol), offset_bytes=self.h.halo[0] * ncol * sz, out=out)
-
-    def close(self, close_handle=True):
-        for b in (self.payload, self.mask, None if self.out_given else self.out):
-            if isinstance(b, _hip.DeviceBuffer):
-                b.free()
-        if close_handle:
-            self.h.close()
-        elif self.incremental and self.sweeps:
-            self.h.set_block_update(0)  # (releases the kept sweep)
 
 
 MAX_ROUNDS = 256  # default bound of the fixpoint iterations below (sharded HAND needs 11 on the roughest test raster)
@@ -477,6 +463,41 @@ def _up_blocks_run(blocks, ncol, dtype, max_iter=MAX_ROUNDS, verify=False):
     return it, bad
 
 
+def _block_handle(d8, nblocks, b, devices):
+    """The handle of row block ``b`` of the host raster ``d8``: its own rows and a halo row towards every neighbour."""
+    nrow, ncol = d8.shape
+    r0, r1 = block_rows(nrow, nblocks)[b]
+    a, e = block_slice(nrow, nblocks, b)
+    return _hip.RasterHandle(d8[a:e], r1 - r0, ncol, device=devices[b], halo=halo_of(b, nblocks))
+
+
+def _run_blocks(d8, nblocks, make, dtype, stream, down, verify, max_iter, out_dtype=None):
+    """The frame of a row-block call: block ``b`` is ``make(b)``, resident, or with ``stream`` (_stream_blocks) a stand-in
+    that builds it for every sweep (``down``: the blocks'); the blocks exchange boundary rows of ``dtype`` until they
+    settle (_up_blocks_run).  The whole result (``out_dtype``, default ``dtype``) is allocated up front and every block
+    fills its own rows — no per-block host arrays, no concatenation (at 8.1 Gcells those were 32-65 GB allocated, copied
+    and freed again: seconds of page faults and munmap).  Returns (result, rounds, bad cells or None)."""
+    import functools
+
+    nrow, ncol = d8.shape
+    rows = block_rows(nrow, nblocks)
+    out = np.empty((nrow, ncol), dtype if out_dtype is None else out_dtype)
+    blocks = []
+    try:
+        for b, (r0, r1) in enumerate(rows):
+            blk = _StreamedBlock(functools.partial(make, b), down, out[r0:r1]) if stream else make(b)
+            blocks.append(blk)
+            blk.relevant = relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks), blk.down)
+        it, bad = _up_blocks_run(blocks, ncol, dtype, max_iter=max_iter, verify=verify)
+        if not stream:
+            for blk, (r0, r1) in zip(blocks, rows):
+                blk.result(out[r0:r1])
+        return out, it, bad
+    finally:
+        for blk in blocks:
+            blk.close()
+
+
 def accuflux_blocks(d8: np.ndarray, nblocks: int, data, nodata_args=(0, 0.0, 0), by_row=False, devices=None,
                     verify=False, max_iter=MAX_ROUNDS, direction="up"):
     """``accuflux(data, direction)`` (reference pyflwdir/streams.py:15-41, :44-70) of a host raster computed as ``nblocks``
@@ -495,24 +516,15 @@ def accuflux_blocks(d8: np.ndarray, nblocks: int, data, nodata_args=(0, 0.0, 0),
         raise NotImplementedError(f"payload dtype {dtype} is not supported by the row-block accuflux")
     data = data.reshape(nrow) if by_row else data.reshape(nrow, ncol)
     devices = devices or [0] * nblocks
-    rows = block_rows(nrow, nblocks)
     dirc = _hip.PFD_UP if direction == "up" else _hip.PFD_DOWN
 
     def make(b):
         a, e = block_slice(nrow, nblocks, b)
-        h = _hip.RasterHandle(d8[a:e], rows[b][1] - rows[b][0], ncol, device=devices[b], halo=halo_of(b, nblocks))
-        return _UpBlock(h, "accuflux", dtype, payload=data[a:e], by_row=by_row, nodata=nodata_args, direction=dirc)
+        return _UpBlock(_block_handle(d8, nblocks, b, devices), "accuflux", dtype, payload=data[a:e], by_row=by_row,
+                        nodata=nodata_args, direction=dirc)
 
-    blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks),
-                                                               down=direction != "up"),
-                        _stream_blocks(d8.size, (1 if by_row else 2) * dtype.itemsize + 28, devices))
-    try:
-        out = _result_array(blocks, rows, ncol, dtype)
-        it, bad = _up_blocks_run(blocks, ncol, dtype, max_iter=max_iter, verify=verify)
-        return _collect(blocks, rows, out), it, bad
-    finally:
-        for blk in blocks:
-            blk.close()
+    return _run_blocks(d8, nblocks, make, dtype, _stream_blocks(d8.size, (1 if by_row else 2) * dtype.itemsize + 28, devices),
+                       dirc == _hip.PFD_DOWN, verify, max_iter)
 
 
 def fillnodata_blocks(d8: np.ndarray, nblocks: int, data, code, nodata_args=(0, 0.0, 0), direction="down",
@@ -529,24 +541,15 @@ def fillnodata_blocks(d8: np.ndarray, nblocks: int, data, code, nodata_args=(0, 
     data = np.asarray(data).reshape(nrow, ncol)
     dtype = data.dtype
     devices = devices or [0] * nblocks
-    rows = block_rows(nrow, nblocks)
     dirc = _hip.PFD_UP if direction == "up" else _hip.PFD_DOWN
 
     def make(b):
         a, e = block_slice(nrow, nblocks, b)
-        h = _hip.RasterHandle(d8[a:e], rows[b][1] - rows[b][0], ncol, device=devices[b], halo=halo_of(b, nblocks))
-        return _UpBlock(h, "fillnodata", dtype, payload=data[a:e], nodata=nodata_args, direction=dirc, code=code, how=how)
+        return _UpBlock(_block_handle(d8, nblocks, b, devices), "fillnodata", dtype, payload=data[a:e], nodata=nodata_args,
+                        direction=dirc, code=code, how=how)
 
-    blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks),
-                                                               down=direction == "up"),
-                        _stream_blocks(d8.size, 2 * dtype.itemsize + 28, devices))
-    try:
-        out = _result_array(blocks, rows, ncol, dtype)
-        it, bad = _up_blocks_run(blocks, ncol, dtype, max_iter=max_iter, verify=verify)
-        return _collect(blocks, rows, out), it, bad
-    finally:
-        for blk in blocks:
-            blk.close()
+    return _run_blocks(d8, nblocks, make, dtype, _stream_blocks(d8.size, 2 * dtype.itemsize + 28, devices),
+                       dirc == _hip.PFD_UP, verify, max_iter)
 
 
 def stream_distance_blocks(d8: np.ndarray, nblocks: int, mask=None, step_lengths=None, devices=None, verify=False,
@@ -561,23 +564,15 @@ def stream_distance_blocks(d8: np.ndarray, nblocks: int, mask=None, step_lengths
     tab = None if step_lengths is None else np.ascontiguousarray(step_lengths, dtype=np.float32).reshape(2 * nrow - 1, 3)
     dtype = np.int32 if tab is None else np.float32
     devices = devices or [0] * nblocks
-    brows = block_rows(nrow, nblocks)
 
     def make(b):
         a, e = block_slice(nrow, nblocks, b)
-        h = _hip.RasterHandle(d8[a:e], brows[b][1] - brows[b][0], ncol, device=devices[b], halo=halo_of(b, nblocks))
         rows = None if tab is None else tab[2 * a:2 * a + 2 * (e - a) - 1]  # (row sums 2a .. 2(e-1): the block's steps)
-        return _UpBlock(h, "distance", dtype, payload=rows, mask=None if mask is None else mask[a:e])
+        return _UpBlock(_block_handle(d8, nblocks, b, devices), "distance", dtype, payload=rows,
+                        mask=None if mask is None else mask[a:e])
 
-    blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks), down=True),
-                        _stream_blocks(d8.size, 4 + (mask is not None) + 28, devices))
-    try:
-        out = _result_array(blocks, brows, ncol, dtype)
-        it, bad = _up_blocks_run(blocks, ncol, dtype, max_iter=max_iter, verify=verify)
-        return _collect(blocks, brows, out), it, bad
-    finally:
-        for blk in blocks:
-            blk.close()
+    return _run_blocks(d8, nblocks, make, dtype, _stream_blocks(d8.size, 4 + (mask is not None) + 28, devices), True,
+                       verify, max_iter)
 
 
 def strahler_blocks(d8: np.ndarray, nblocks: int, mask=None, devices=None, verify=False, max_iter=MAX_ROUNDS):
@@ -590,53 +585,29 @@ def strahler_blocks(d8: np.ndarray, nblocks: int, mask=None, devices=None, verif
     if mask is not None:
         mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(nrow, ncol)
     devices = devices or [0] * nblocks
-    brows = block_rows(nrow, nblocks)
 
     def make(b):
         a, e = block_slice(nrow, nblocks, b)
-        h = _hip.RasterHandle(d8[a:e], brows[b][1] - brows[b][0], ncol, device=devices[b], halo=halo_of(b, nblocks))
-        return _UpBlock(h, "strahler", np.uint8, mask=None if mask is None else mask[a:e])
+        return _UpBlock(_block_handle(d8, nblocks, b, devices), "strahler", np.uint8, mask=None if mask is None else mask[a:e])
 
-    blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks), down=False),
-                        _stream_blocks(d8.size, 1 + (mask is not None) + 28, devices))
-    try:
-        out = _result_array(blocks, brows, ncol, np.uint8)
-        it, bad = _up_blocks_run(blocks, ncol, np.uint8, max_iter=max_iter, verify=verify)
-        return _collect(blocks, brows, out), it, bad
-    finally:
-        for blk in blocks:
-            blk.close()
+    return _run_blocks(d8, nblocks, make, np.uint8, _stream_blocks(d8.size, 1 + (mask is not None) + 28, devices),
+                       False, verify, max_iter)
 
 
-class _ClassicBlock(_SeedGate):
-    """Device-resident state of one row block of the classic stream order between the exchanges: the per-cell byte of
-    pfd_trib_info_block (halo rows from the neighbours), the mask and the orders stay in HBM."""
+class _ClassicBlock(_Block):
+    """One row block of the classic stream order: the per-cell byte of pfd_trib_info_block (halo rows from the
+    neighbours), the mask and the orders stay in HBM."""
+
+    down = True
 
     def __init__(self, handle, tinfo_rows, mask_rows):
-        self.h = handle
-        ncol, dev = handle.ncol, handle.device
-        self.nrows_dev = handle.nrow + sum(handle.halo)
-        self.tinfo = _hip.DeviceBuffer(tinfo_rows.nbytes, dev).upload(np.ascontiguousarray(tinfo_rows))
-        self.mask = None if mask_rows is None else _hip.DeviceBuffer(mask_rows.nbytes, dev).upload(np.ascontiguousarray(mask_rows))
-        self.out = _hip.DeviceBuffer(self.nrows_dev * ncol, dev)
-        self.swept_with, self.brows = None, None
+        super().__init__(handle, np.uint8)
+        self.tinfo = self._upload(tinfo_rows)
+        self.mask = None if mask_rows is None else self._upload(mask_rows)
+        self._result_buffer()
 
     def _call(self, seed, verify):
         return self.h.stream_order_classic_block(self.tinfo, self.mask, seed, self.out, verify=verify, memspace=_hip.PFD_DEVICE)
-
-    def verify(self, seed):
-        return self._call(seed, True)[1]
-
-    def result(self, out=None):
-        ncol = self.h.ncol
-        return self.out.download(np.uint8, (self.h.nrow, ncol), offset_bytes=self.h.halo[0] * ncol, out=out)
-
-    def close(self, close_handle=True):
-        for b in (self.tinfo, self.mask, self.out):
-            if b is not None:
-                b.free()
-        if close_handle:
-            self.h.close()
 
 
 def classic_blocks(d8: np.ndarray, nblocks: int, uparea, mask=None, upa_min=0.0, devices=None, verify=False,
@@ -656,19 +627,13 @@ def classic_blocks(d8: np.ndarray, nblocks: int, uparea, mask=None, upa_min=0.0,
     if mask is not None:
         mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(nrow, ncol)
     devices = devices or [0] * nblocks
-    brows = block_rows(nrow, nblocks)
     stream = _stream_blocks(d8.size, 3 + uparea.dtype.itemsize + 28, devices)
-
-    def handle(b):
-        a, e = block_slice(nrow, nblocks, b)
-        return _hip.RasterHandle(d8[a:e], brows[b][1] - brows[b][0], ncol, device=devices[b], halo=halo_of(b, nblocks))
-
-    handles, blocks = {}, []
+    handles = {}
     try:
         infos = []
         for b in range(nblocks):
             a, e = block_slice(nrow, nblocks, b)
-            h = handle(b)
+            h = _block_handle(d8, nblocks, b, devices)
             try:
                 infos.append(h.trib_info_block(uparea[a:e], _hip._PAYLOAD_CODE[uparea.dtype], None if mask is None else mask[a:e],
                                                upa_min).reshape(e - a, ncol))
@@ -686,62 +651,47 @@ def classic_blocks(d8: np.ndarray, nblocks: int, uparea, mask=None, upa_min=0.0,
 
         def make(b):
             a, e = block_slice(nrow, nblocks, b)
-            return _ClassicBlock(handles.pop(b) if b in handles else handle(b), infos[b], None if mask is None else mask[a:e])
+            h = handles.pop(b) if b in handles else _block_handle(d8, nblocks, b, devices)
+            return _ClassicBlock(h, infos[b], None if mask is None else mask[a:e])
 
-        blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks),
-                                                                   down=True), stream)
-        out = _result_array(blocks, brows, ncol, np.uint8)
-        it, bad = _up_blocks_run(blocks, ncol, np.uint8, max_iter=max_iter, verify=verify)
-        return _collect(blocks, brows, out), it, bad
+        return _run_blocks(d8, nblocks, make, np.uint8, stream, True, verify, max_iter)
     finally:
         for h in handles.values():
             h.close()
-        for blk in blocks:
-            blk.close()
 
 
-class _FloodBlock(_SeedGate):
-    """Device-resident state of one row block of dem.floodplains between the exchanges: elevation, stream flags, height
-    thresholds and the floodplain state (16 bytes per cell) stay in HBM; only the two boundary rows of the state travel."""
+class _FloodBlock(_Block):
+    """One row block of dem.floodplains: elevation, stream flags, height thresholds and the floodplain state (``out``, 16
+    bytes per cell) stay in HBM; only the two boundary rows of the state travel."""
+
+    down = True
 
     def __init__(self, handle, elevtn_rows, elev_code, is_stream_rows, stream_h_rows, pool=None):
-        self.h, self.code = handle, elev_code
+        super().__init__(handle, _hip.FLOOD_STATE)
+        self.code = elev_code
         ncol, dev = handle.ncol, handle.device
-        self.nrows_dev = handle.nrow + sum(handle.halo)
         # ``pool`` (streamed blocks: {"rows": the most device rows any block has}): the four buffers are allocated once
         # for the largest block and serve every block of the call — a hipMalloc of tens of GB takes longer than filling it
-        self.pool = pool
 
         def buf(name, bytes_per_cell):
             if pool is None:
-                return _hip.DeviceBuffer(self.nrows_dev * ncol * bytes_per_cell, dev)
+                return self._own(_hip.DeviceBuffer(self.nrows_dev * ncol * bytes_per_cell, dev))
             if name not in pool:
                 pool[name] = _hip.DeviceBuffer(max(pool["rows"], self.nrows_dev) * ncol * bytes_per_cell, dev)
             return pool[name]
 
         up = lambda name, a: buf(name, a.dtype.itemsize).upload(np.ascontiguousarray(a))  # noqa: E731
         self.elev, self.stream, self.hs = up("elev", elevtn_rows), up("stream", is_stream_rows), up("hs", stream_h_rows)
-        self.state = buf("state", _hip.FLOOD_STATE.itemsize)
-        self.swept_with, self.brows = None, None
+        self.out = buf("state", _hip.FLOOD_STATE.itemsize)
 
     def _call(self, seed, verify):
-        return self.h.floodplains_block(self.elev, self.code, self.stream, self.hs, seed, self.state, verify=verify,
+        return self.h.floodplains_block(self.elev, self.code, self.stream, self.hs, seed, self.out, verify=verify,
                                         memspace=_hip.PFD_DEVICE)
-
-    def verify(self, seed):
-        return self._call(seed, True)[1]
 
     def result(self, out=None):
         """int8 flags of the own rows (``out``: the block's rows of the whole result, filled in place) — extracted from the
         16-byte state records on the device (pfd_floodplains_block_flags): 1 byte per cell crosses PCIe."""
-        return self.h.floodplains_block_flags(self.state, out)
-
-    def close(self, close_handle=True):
-        if self.pool is None:
-            for b in (self.elev, self.stream, self.hs, self.state):
-                b.free()
-        if close_handle:
-            self.h.close()
+        return self.h.floodplains_block_flags(self.out, out)
 
 
 def floodplains_blocks(d8: np.ndarray, nblocks: int, elevtn, is_stream, stream_h, devices=None, verify=False,
@@ -760,31 +710,17 @@ def floodplains_blocks(d8: np.ndarray, nblocks: int, elevtn, is_stream, stream_h
     is_stream = np.ascontiguousarray(is_stream, dtype=np.uint8).reshape(nrow, ncol)
     stream_h = np.ascontiguousarray(stream_h, dtype=np.float32).reshape(nrow, ncol)
     devices = devices or [0] * nblocks
-    brows = block_rows(nrow, nblocks)
-
     stream = _stream_blocks(d8.size, elevtn.dtype.itemsize + 5 + 2 * _hip.FLOOD_STATE.itemsize + 28, devices)
     pool = {"rows": max(e - a for a, e in (block_slice(nrow, nblocks, b) for b in range(nblocks)))} if stream else None
 
     def make(b):
         a, e = block_slice(nrow, nblocks, b)
-        h = _hip.RasterHandle(d8[a:e], brows[b][1] - brows[b][0], ncol, device=devices[b], halo=halo_of(b, nblocks))
-        return _FloodBlock(h, elevtn[a:e], _ELEV_CODE[elevtn.dtype], is_stream[a:e], stream_h[a:e], pool=pool)
+        return _FloodBlock(_block_handle(d8, nblocks, b, devices), elevtn[a:e], _ELEV_CODE[elevtn.dtype], is_stream[a:e],
+                           stream_h[a:e], pool=pool)
 
-    blocks = _blocks_of(nblocks, make, lambda b: relevant_halo(d8[slice(*block_slice(nrow, nblocks, b))], halo_of(b, nblocks), down=True),
-                        stream)
     try:
-        out = np.empty((nrow, ncol), np.int8)  # (every block writes its own rows: no concatenation of 8 GB at 8.1 Gcells)
-        for b, blk in enumerate(blocks):
-            if isinstance(blk, _StreamedBlock):
-                blk.into = out[brows[b][0]:brows[b][1]]
-        it, bad = _up_blocks_run(blocks, ncol, _hip.FLOOD_STATE, max_iter=max_iter, verify=verify)
-        for b, blk in enumerate(blocks):
-            if not isinstance(blk, _StreamedBlock):
-                blk.result(out[brows[b][0]:brows[b][1]])
-        return out, it, bad
+        return _run_blocks(d8, nblocks, make, _hip.FLOOD_STATE, stream, True, verify, max_iter, out_dtype=np.int8)
     finally:
-        for blk in blocks:
-            blk.close()
         for b in (pool or {}).values():
             if isinstance(b, _hip.DeviceBuffer):
                 b.free()
@@ -1220,10 +1156,9 @@ class DistributedRaster:
         blk, err, it = None, None, 0
         try:
             blk = make_block()
-            if getattr(self, "_edge", None) is not None and isinstance(blk, _UpBlock):  # (host transport: a rank sweeps again only when a halo value it depends on changed;
+            if getattr(self, "_edge", None) is not None and isinstance(blk, _Block):  # (host transport: a rank sweeps again only when a halo value it depends on changed;
                 #  the RCCL loop counts every changed halo value on the device)
-                down = blk.kind == "distance" or (blk.kind == "accuflux" and blk.direction == _hip.PFD_DOWN)
-                blk.relevant = relevant_halo(self._edge, self.handle.halo, down)
+                blk.relevant = relevant_halo(self._edge, self.handle.halo, blk.down)
         except Exception as exc:  # noqa: BLE001 - the failure travels with the agreement: nobody is left waiting
             err = exc
         if self.comm is not None:
