@@ -446,6 +446,38 @@ int pfd_fill_depressions(int dtype, const void *elevtn, int64_t nrow, int64_t nc
  * engine's 32-bit order) — as does pfd_basins, which otherwise runs at any size too. */
 int pfd_ucat_area(pfd_raster *h, const int64_t *idxs_out, int64_t k, int map_dtype, void *map_out, int memspace,
                   int area_dtype, const void *area_rows, void *area_out);
+/* ---- outlets derived from the network: mark -> list in sequence order -> (number, fill) -----------------------------
+ * Three calls of the reference are one primitive (csrc/outlets.hip): mark cells by a rule that looks at the cell and its
+ * downstream cell, list the marked cells in the order of core.idxs_seq (only cells IN the sequence count: a cell on or
+ * above a cycle is never an outlet, as in the reference, whose loops run over `seq`), and for the sub-basins number the
+ * list 1..k and fill the numbers upstream with the label query of pfd_basins.  The sequence stays on the device.
+ * Common arguments: `idx_dtype` (PFD_I32 / PFD_U32 / PFD_I64) is the type of `idxs_out`, which has room for `cap`
+ * entries; *k_out receives the number of outlets.  k > cap is NOT an error: PFD_OK, the list (and `lbs_out`) are left
+ * unwritten, everything else is complete — the caller repeats the call with cap >= k.  `memspace` covers the per-cell
+ * input, the per-cell output and the lists alike.  On D8 handles of any size (beyond 2^32 - 2 cells over the 64-bit
+ * sequence of csrc/order64.hip; PFD_EUNSUPPORTED there for a raster with cycles, like pfd_basins) and on general
+ * idxs_ds handles (over their installed order, if any); not on row-block handles.
+ *
+ * pfd_subbasins_streamorder — basins.subbasins_streamorder (reference pyflwdir/basins.py:67-103; FlwdirRaster.
+ *   subbasins_streamorder pyflwdir.py:601-629): `strord` holds n values of `dtype` (PFD_U8, PFD_I32, PFD_U32 or PFD_I64);
+ *   a cell is an outlet iff strord >= min_sto and (it is a pit or its downstream cell has another strord); outlets are
+ *   listed in REVERSED sequence order; map_out: n int32, the list position + 1 of the first outlet on the cell's
+ *   downstream path (itself included), 0 if there is none.  min_sto is taken as given (the reference's negative form,
+ *   max(strord) + min_sto, is the caller's to resolve).
+ * pfd_outflow_idxs — core.outflow_idxs (core.py:501-514; FlwdirRaster.outflow_idxs pyflwdir.py:820-835): `region` uint8
+ *   (!= 0 inside); the cells of the region that are a pit or drain to a cell outside it, and have no other such cell
+ *   further down their flow path (one label fill of the candidates); FORWARD sequence order.
+ * pfd_basin_outlets — regions.region_outlets (regions.py:129-163; FlwdirRaster.basin_outlets pyflwdir.py:720-740):
+ *   `regions` holds n labels of `dtype` (PFD_I32, PFD_U32, PFD_I64 or PFD_U64); a cell is an outlet iff its label is > 0
+ *   and (it is a pit or its downstream cell has another label).  lbs_out (cap labels of `dtype`) and idxs_out are
+ *   sorted by label; outlets of one label keep their reversed sequence order (the reference sorts with an unstable
+ *   argsort: their order is unspecified there). */
+int pfd_subbasins_streamorder(pfd_raster *h, int dtype, const void *strord, int64_t min_sto, int idx_dtype, void *idxs_out,
+                              int64_t cap, int64_t *k_out, int32_t *map_out, int memspace);
+int pfd_outflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dtype, void *idxs_out, int64_t cap, int64_t *k_out,
+                     int memspace);
+int pfd_basin_outlets(pfd_raster *h, int dtype, const void *regions, int idx_dtype, void *idxs_out, void *lbs_out,
+                      int64_t cap, int64_t *k_out, int memspace);
 /* dem.floodplains (reference pyflwdir/dem.py:333-379; FlwdirRaster.floodplains pyflwdir.py:1513-1545):
  * `is_stream` uint8 (1 where uparea >= upa_min), `stream_h` float32 (uparea ** b on those cells — evaluated by
  * the caller in the reference's dtype), elevtn PFD_F32 / PFD_F64; out int8: 1 floodplain, 0 not, -1 off the sequence. */

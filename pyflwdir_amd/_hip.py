@@ -46,6 +46,7 @@ SYMBOLS = [
     "pfd_reserve", "pfd_alloc_stats", "pfd_mem_info", "pfd_transfer_stats", "pfd_count_nonfinite", "pfd_floodplains_block", "pfd_trib_info_block",
     "pfd_stream_order_classic_block", "pfd_upstream_area_rows_fixed", "pfd_floodplains_block_flags",
     "pfd_fillnodata", "pfd_fillnodata_block",
+    "pfd_subbasins_streamorder", "pfd_outflow_idxs", "pfd_basin_outlets",
 ]
 
 _lib = None
@@ -108,6 +109,11 @@ def lib() -> C.CDLL:
                                      C.c_void_p, C.c_int]
         L.pfd_fillnodata_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
+        L.pfd_subbasins_streamorder.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                                C.POINTER(C.c_int64), C.c_void_p, C.c_int]
+        L.pfd_outflow_idxs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]
+        L.pfd_basin_outlets.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.POINTER(C.c_int64), C.c_int]
         L.pfd_stream_distance_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.pfd_strahler_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -643,6 +649,56 @@ class RasterHandle:
         check(lib().pfd_ucat_area(self._h, ptr(idxs_out), idxs_out.size, IDX_CODE[np.dtype(map_dtype)], ptr(ucmap), PFD_HOST,
                                   code, ptr(area_rows), ptr(are)))
         return ucmap, are
+
+    # -- outlets derived from the network (csrc/outlets.hip) ------------------------------------------------------
+    def _outlet_cap(self):
+        """Room for the outlet list of a first call: the C entry points report the count and leave the list unwritten when
+        it does not fit; the call is then repeated with room for all of them."""
+        return max(4096, self.n // 16)
+
+    def subbasins_streamorder(self, strord, dtype_code, min_sto, idx_dtype, cap=None, out=None, idxs_out=None,
+                              memspace=PFD_HOST):
+        """(int32 map[n], outlet cells[k]) of pfd_subbasins_streamorder.  PFD_DEVICE: ``strord``, ``out`` and ``idxs_out``
+        (``cap`` entries) are DeviceBuffers; returns (out, idxs_out, k)."""
+        k = C.c_int64(0)
+        if memspace != PFD_HOST:
+            check(lib().pfd_subbasins_streamorder(self._h, int(dtype_code), ptr(strord), int(min_sto),
+                                                  IDX_CODE[np.dtype(idx_dtype)], ptr(idxs_out), int(cap), C.byref(k), ptr(out),
+                                                  memspace))
+            return out, idxs_out, int(k.value)
+        out = np.empty(self.n, np.int32)
+        cap = self._outlet_cap() if cap is None else int(cap)
+        while True:
+            idxs = np.empty(cap, idx_dtype)
+            check(lib().pfd_subbasins_streamorder(self._h, int(dtype_code), ptr(strord), int(min_sto),
+                                                  IDX_CODE[np.dtype(idx_dtype)], ptr(idxs), cap, C.byref(k), ptr(out), PFD_HOST))
+            if k.value <= cap:
+                return out, idxs[:k.value].copy()
+            cap = int(k.value)
+
+    def outflow_idxs(self, region, idx_dtype, cap=None):
+        """Outflow cells of a uint8 region mask in forward sequence order (pfd_outflow_idxs)."""
+        k = C.c_int64(0)
+        cap = self._outlet_cap() if cap is None else int(cap)
+        while True:
+            idxs = np.empty(cap, idx_dtype)
+            check(lib().pfd_outflow_idxs(self._h, ptr(region), IDX_CODE[np.dtype(idx_dtype)], ptr(idxs), cap, C.byref(k),
+                                         PFD_HOST))
+            if k.value <= cap:
+                return idxs[:k.value].copy()
+            cap = int(k.value)
+
+    def basin_outlets(self, regions, dtype_code, idx_dtype, cap=None):
+        """(labels[k] in the dtype of ``regions``, outlet cells[k]) sorted by label (pfd_basin_outlets)."""
+        k = C.c_int64(0)
+        cap = self._outlet_cap() if cap is None else int(cap)
+        while True:
+            idxs, lbs = np.empty(cap, idx_dtype), np.empty(cap, regions.dtype)
+            check(lib().pfd_basin_outlets(self._h, int(dtype_code), ptr(regions), IDX_CODE[np.dtype(idx_dtype)], ptr(idxs),
+                                          ptr(lbs), cap, C.byref(k), PFD_HOST))
+            if k.value <= cap:
+                return lbs[:k.value].copy(), idxs[:k.value].copy()
+            cap = int(k.value)
 
     def floodplains(self, elevtn, elev_code, is_stream, stream_h):
         out = np.empty(self.n, np.int8)

@@ -536,6 +536,13 @@ int pfd_gen_idxs_ds(pfd_raster *h, int idx_dtype, void *out, int memspace) {
   return o.finish(h->stream);
 }
 int pfd_gen_order(pfd_raster *h) { return gen_order(h); }
+// the ordered graph on the device, for callers that walk it themselves (outlets.hip): downstream links (0xFFFFFFFF =
+// nodata, own index = pit) and the h->n_seq cells of the (installed) sequence
+int pfd_gen_graph_dev(pfd_raster *h, const u32 **ds, const u32 **seq) {
+  PFDCHK(gen_order(h));
+  *ds = G(h)->ds, *seq = G(h)->seq;
+  return PFD_OK;
+}
 int pfd_gen_idxs_seq(pfd_raster *h, int idx_dtype, void *out, int memspace) {
   PFDCHK(gen_order(h));
   return pfd_export_u32(h, G(h)->seq, h->n_seq, idx_dtype, out, memspace);

@@ -1,0 +1,360 @@
+// outlets.hip — outlets derived from the network itself: basins.subbasins_streamorder (reference pyflwdir/basins.py:67-103),
+// core.outflow_idxs (core.py:501-514) and regions.region_outlets (regions.py:129-163).
+//
+// The three serial loops of the reference are one primitive:
+//   mark    one thread per cell decides from the cell's value and its downstream cell's value whether it is an outlet;
+//   list    the marked cells in the order of core.idxs_seq — a stable compaction OF THE SEQUENCE (rocprim select with the
+//           mark as predicate), so a cell that is not in the sequence (on or above a cycle) is never listed, as in the
+//           reference, whose loops run over `seq`; two of the loops walk the sequence backwards: the list is reversed;
+//   fill    (sub-basins) the list positions + 1 are the labels of the label query behind pfd_basins (pfd_basins_dev):
+//           core.fillnodata_upstream over nested outlets is "the first outlet on the downstream path".
+// outflow_idxs has one more step: its `mask`, inherited from the downstream cell and cleared at every listed cell, says
+// "no listed cell further down the path" — and since the lowest candidate of a path is always listed, that is "no
+// CANDIDATE further down": one label fill of the candidate flags, then every candidate looks at its downstream cell.
+// The sequence comes from the engine the handle already has — pfd_exact_seq_dev (32-bit cells), the 64-bit queue of
+// order64.hip, the (installed) order of a general graph — and never leaves the device.
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
+#include <algorithm>
+#include <type_traits>
+
+#include "common.h"
+
+int pfd_gen_graph_dev(pfd_raster *h, const u32 **ds, const u32 **seq);  // general.hip: orders the graph
+
+namespace {
+
+enum { R_STO = 0, R_REGION = 1, R_LABEL = 2 };
+
+// the downstream link under the three forms of a handle: valid(x), down(x) (own index for a pit)
+struct DownD8 {
+  const u8 *ncode;
+  Geo g;
+  __device__ __forceinline__ bool valid(u64 x) const { return ncode[x] != D8_MV; }
+  __device__ __forceinline__ u64 down(u64 x) const { return d8_down(g, (u32)x, ncode[x]); }
+};
+struct DownWide {  // beyond 2^32 - 2 cells
+  const u8 *ncode;
+  i64 ncol;
+  __device__ __forceinline__ bool valid(u64 x) const { return ncode[x] != D8_MV; }
+  __device__ __forceinline__ u64 down(u64 x) const {
+    const u32 code = ncode[x];
+    if (!d8_is_dir(code)) return x;
+    const int k = d8_slot(code);
+    return (u64)((i64)x + (i64)d8_dr(k) * ncol + d8_dc(k));
+  }
+};
+struct DownGen {  // general idxs_ds graph: 0xFFFFFFFF = nodata
+  const u32 *ds;
+  __device__ __forceinline__ bool valid(u64 x) const { return ds[x] != 0xFFFFFFFFu; }
+  __device__ __forceinline__ u64 down(u64 x) const { return ds[x]; }
+};
+
+template <class T>
+__device__ __forceinline__ bool at_least(T a, i64 m) {
+  if (std::is_unsigned<T>::value) return m <= 0 || (u64)a >= (u64)m;
+  return (i64)a >= m;
+}
+
+// mark[x] = the cell-local rule; *count += marked cells (one atomic per wave that holds any)
+template <int RULE, class T, class D>
+__global__ void __launch_bounds__(256) k_mark(const D d, u64 n, const T *__restrict__ v, i64 min_sto, u8 *__restrict__ mark,
+                                              unsigned long long *__restrict__ count) {
+  // (grid-stride in whole workgroups: n may exceed the 2^32 threads one launch dimension runs)
+  for (u64 x0 = (u64)blockIdx.x * 256u; x0 < n; x0 += (u64)gridDim.x * 256u) {
+    const u64 x = x0 + threadIdx.x;
+    bool m = false;
+    if (x < n && d.valid(x)) {
+      const u64 y = d.down(x);
+      const T a = v[x];
+      if (RULE == R_STO) m = at_least<T>(a, min_sto) && (y == x || v[y] != a);
+      else if (RULE == R_REGION) m = a != T(0) && (y == x || v[y] == T(0));
+      else m = a > T(0) && (y == x || v[y] != a);
+    }
+    if (x < n) mark[x] = m ? 1 : 0;
+    const u64 b = __ballot(m);
+    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
+  }
+}
+// outflow_idxs: a candidate with a candidate at or below its downstream cell (lab != 0 there) is dropped
+template <class D>
+__global__ void __launch_bounds__(256) k_drop_shadowed(const D d, u64 n, const u8 *__restrict__ lab, u8 *__restrict__ mark,
+                                                       unsigned long long *__restrict__ count) {
+  for (u64 x0 = (u64)blockIdx.x * 256u; x0 < n; x0 += (u64)gridDim.x * 256u) {
+    const u64 x = x0 + threadIdx.x;
+    bool m = false;
+    if (x < n && mark[x]) {
+      const u64 y = d.down(x);
+      m = y == x || lab[y] == 0;
+      if (!m) mark[x] = 0;
+    }
+    const u64 b = __ballot(m);
+    if ((threadIdx.x & 63u) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
+  }
+}
+struct IsMarked {
+  const u8 *mark;
+  template <class I>
+  __host__ __device__ bool operator()(const I &x) const { return mark[x] != 0; }
+};
+// the list as the reference appends it (reversed: the loops over seq[::-1]) in 64-bit indices, and its numbers 1..k
+template <class I>
+__global__ void __launch_bounds__(256) k_number(const I *__restrict__ sel, u64 k, bool reversed, i64 *__restrict__ idx,
+                                                u32 *__restrict__ ids) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= k) return;
+  idx[i] = (i64)sel[reversed ? k - 1 - i : i];
+  ids[i] = (u32)(i + 1);
+}
+template <class T>
+__global__ void __launch_bounds__(256) k_gather(const i64 *__restrict__ idx, u64 k, const T *__restrict__ v, T *__restrict__ out) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i < k) out[i] = v[idx[i]];
+}
+template <class O>
+__global__ void __launch_bounds__(256) k_export_i64(const i64 *__restrict__ idx, u64 k, O *__restrict__ out) {
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i < k) out[i] = (O)idx[i];
+}
+
+static inline u32 sweep_grid(u64 n) { return (u32)std::min<u64>((n + 255) / 256, 1u << 22); }
+
+struct Outlets {  // the numbered list on the device
+  DevBuf idx, ids;  // k x i64 cells in the reference's list order, k x u32 numbers 1..k
+  u64 k = 0;
+};
+
+static int read_count(pfd_raster *h, const unsigned long long *dev, u64 *out) {
+  unsigned long long v = 0;
+  HIPCHK(hipMemcpyAsync(&v, dev, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *out = (u64)v;
+  return PFD_OK;
+}
+
+// compaction of the cells [0, n) / of the sequence by the mark; `out` has room for `room` entries (>= what is marked)
+template <class In, class Out>
+static int select_marked(pfd_raster *h, In in, u64 m, const u8 *mark, Out *out, unsigned long long *count_dev) {
+  size_t tb = 0;
+  HIPCHK(rocprim::select(nullptr, tb, in, out, count_dev, (size_t)m, IsMarked{mark}, h->stream));
+  DevBuf tmp;
+  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
+  HIPCHK(rocprim::select(tmp.p, tb, in, out, count_dev, (size_t)m, IsMarked{mark}, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (`tmp` is released on return)
+  return PFD_OK;
+}
+
+template <int RULE, class T, class D, class I>
+static int outlets_run(pfd_raster *h, const D &d, const I *seq, u64 m, const T *v, i64 min_sto, bool reversed, Outlets &R) {
+  const u64 n = (u64)h->n;
+  DevBuf mark, cnt;
+  PFDCHK(mark.alloc((size_t)n));
+  PFDCHK(cnt.alloc(4 * sizeof(unsigned long long)));
+  unsigned long long *c = cnt.as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(c, 0, 4 * sizeof(unsigned long long), h->stream));
+  pfd_seg_begin(h, "outlets_mark");
+  k_mark<RULE, T, D><<<sweep_grid(n), 256, 0, h->stream>>>(d, n, v, min_sto, mark.as<u8>(), c);
+  KCHK();
+  pfd_seg_end(h, 1);
+  u64 marked = 0;
+  PFDCHK(read_count(h, c, &marked));
+  if (RULE == R_REGION && marked) {
+    if (marked >= 0xFFFFFFFFull) {
+      pfd_set_error("outflow_idxs: %llu candidate cells are more than the label fill takes", (unsigned long long)marked);
+      return PFD_EUNSUPPORTED;
+    }
+    DevBuf cand, ones, lab;
+    PFDCHK(cand.alloc((size_t)marked * sizeof(i64)));
+    PFDCHK(ones.alloc((size_t)marked));
+    PFDCHK(lab.alloc((size_t)n + 64));
+    PFDCHK(select_marked(h, rocprim::counting_iterator<i64>(0), n, mark.as<u8>(), cand.as<i64>(), c + 1));
+    HIPCHK(hipMemsetAsync(ones.p, 1, (size_t)marked, h->stream));
+    PFDCHK(pfd_basins_dev(h, cand.as<i64>(), ones.p, (u32)marked, 1, lab.p));
+    pfd_seg_begin(h, "outlets_drop_shadowed");
+    k_drop_shadowed<D><<<sweep_grid(n), 256, 0, h->stream>>>(d, n, lab.as<u8>(), mark.as<u8>(), c + 2);
+    KCHK();
+    pfd_seg_end(h, 1);
+    PFDCHK(read_count(h, c + 2, &marked));
+  }
+  R.k = 0;
+  if (!marked || !m) return PFD_OK;
+  DevBuf sel;
+  PFDCHK(sel.alloc((size_t)marked * sizeof(I)));
+  pfd_seg_begin(h, "outlets_list");
+  PFDCHK(select_marked(h, seq, m, mark.as<u8>(), sel.as<I>(), c + 3));
+  PFDCHK(read_count(h, c + 3, &R.k));
+  if (R.k) {
+    PFDCHK(R.idx.alloc((size_t)R.k * sizeof(i64)));
+    PFDCHK(R.ids.alloc((size_t)R.k * sizeof(u32)));
+    k_number<I><<<cdiv_u32(R.k, 256), 256, 0, h->stream>>>(sel.as<I>(), R.k, reversed, R.idx.as<i64>(), R.ids.as<u32>());
+    KCHK();
+  }
+  pfd_seg_end(h, 3);
+  HIPCHK(hipStreamSynchronize(h->stream));  // (`sel` and `mark` are released on return)
+  return PFD_OK;
+}
+
+// the handle's own sequence and downstream links
+template <int RULE, class T>
+static int outlets_of(pfd_raster *h, const T *v, i64 min_sto, bool reversed, Outlets &R) {
+  if (h->gen) {
+    const u32 *ds = nullptr, *seq = nullptr;
+    PFDCHK(pfd_gen_graph_dev(h, &ds, &seq));
+    return outlets_run<RULE, T>(h, DownGen{ds}, seq, (u64)h->n_seq, v, min_sto, reversed, R);
+  }
+  if (pfd_wide_cells(h)) {
+    DevBuf q;
+    u64 nseq = 0;
+    PFDCHK(pfd_wide_seq_dev(h, q, &nseq));
+    return outlets_run<RULE, T>(h, DownWide{h->ncode, h->ncol}, (const u64 *)q.p, nseq, v, min_sto, reversed, R);
+  }
+  DevBuf oseq;
+  PFDCHK(pfd_exact_seq_dev(h, oseq));
+  return outlets_run<RULE, T>(h, DownD8{h->ncode, h->geo}, (const u32 *)oseq.p, (u64)h->n_seq, v, min_sto, reversed, R);
+}
+
+static size_t idx_bytes(int idx_dtype) { return idx_dtype == PFD_I64 ? 8 : (idx_dtype == PFD_I32 || idx_dtype == PFD_U32) ? 4 : 0; }
+
+// k values from HBM into the caller's list (a host list: counted as a download of the call)
+static int give_list(pfd_raster *h, const void *dev, size_t bytes, void *out, int memspace) {
+  if (!bytes) return PFD_OK;
+  if (memspace == PFD_DEVICE) {
+    HIPCHK(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return PFD_OK;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const double t0 = pfd_now_ms();
+  HIPCHK(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  PfdTransfer &t = pfd_transfer();
+  t.d2h_bytes += (double)bytes, t.d2h_ms += pfd_now_ms() - t0, t.host_results += 1;
+  return PFD_OK;
+}
+
+static int give_idxs(pfd_raster *h, const i64 *idx, u64 k, int idx_dtype, void *out, int memspace) {
+  if (!k) return PFD_OK;
+  if (idx_dtype == PFD_I64) return give_list(h, idx, (size_t)k * 8, out, memspace);
+  DevBuf tmp;
+  PFDCHK(tmp.alloc((size_t)k * 4));
+  if (idx_dtype == PFD_I32) k_export_i64<i32><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(idx, k, tmp.as<i32>());
+  else k_export_i64<u32><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(idx, k, tmp.as<u32>());
+  KCHK();
+  return give_list(h, tmp.p, (size_t)k * 4, out, memspace);
+}
+
+static int check_common(pfd_raster *h, const char *what, const void *data, int idx_dtype, const void *idxs_out, i64 cap,
+                        const i64 *k_out) {
+  PFDCHK(pfd_check_handle(h));
+  PFDCHK(pfd_require_unblocked(h, what));
+  if (!data || !k_out || cap < 0 || (cap > 0 && !idxs_out) || !idx_bytes(idx_dtype)) {
+    pfd_set_error("%s: bad arguments (NULL pointer, cap=%lld, index dtype %d)", what, (long long)cap, idx_dtype);
+    return PFD_EINVAL;
+  }
+  if (h->n > 4294967294ll && idx_dtype != PFD_I64) {
+    pfd_set_error("%s of a raster of %lld cells needs the int64 index dtype (PFD_I64)", what, (long long)h->n);
+    return PFD_EINVAL;
+  }
+  pfd_seg_clear(h);
+  return PFD_OK;
+}
+
+template <class T>
+static int streamorder_t(pfd_raster *h, const void *strord, i64 min_sto, int idx_dtype, void *idxs_out, i64 cap, i64 *k_out,
+                         i32 *map_out, int memspace) {
+  InArg v;
+  PFDCHK(v.bind(strord, (size_t)h->n * sizeof(T), memspace, h->stream));
+  OutArg o;
+  PFDCHK(o.bind(map_out, (size_t)h->n * sizeof(i32), memspace));
+  Outlets R;
+  PFDCHK((outlets_of<R_STO, T>(h, (const T *)v.dev, min_sto, true, R)));
+  if (R.k > 0x7FFFFFFFull) {
+    pfd_set_error("subbasins_streamorder: %llu outlets do not fit the int32 map", (unsigned long long)R.k);
+    return PFD_EUNSUPPORTED;
+  }
+  PFDCHK(pfd_basins_dev(h, R.idx.as<i64>(), R.ids.p, (u32)R.k, 4, o.dev));
+  *k_out = (i64)R.k;
+  if ((i64)R.k <= cap) PFDCHK(give_idxs(h, R.idx.as<i64>(), R.k, idx_dtype, idxs_out, memspace));
+  return o.finish(h->stream);
+}
+
+template <class T>
+static int basin_outlets_t(pfd_raster *h, const void *regions, int idx_dtype, void *idxs_out, void *lbs_out, i64 cap,
+                           i64 *k_out, int memspace) {
+  InArg v;
+  PFDCHK(v.bind(regions, (size_t)h->n * sizeof(T), memspace, h->stream));
+  Outlets R;
+  PFDCHK((outlets_of<R_LABEL, T>(h, (const T *)v.dev, 0, true, R)));
+  *k_out = (i64)R.k;
+  if (!R.k || (i64)R.k > cap) return PFD_OK;
+  // by label, stable: the outlets of one label stay in reversed sequence order
+  const u64 k = R.k;
+  DevBuf lb, lb2, idx2, tmp;
+  PFDCHK(lb.alloc((size_t)k * sizeof(T)));
+  PFDCHK(lb2.alloc((size_t)k * sizeof(T)));
+  PFDCHK(idx2.alloc((size_t)k * sizeof(i64)));
+  pfd_seg_begin(h, "outlets_sort");
+  k_gather<T><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(R.idx.as<i64>(), k, (const T *)v.dev, lb.as<T>());
+  KCHK();
+  size_t tb = 0;
+  HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, lb.as<T>(), lb2.as<T>(), R.idx.as<i64>(), idx2.as<i64>(), (size_t)k, 0u,
+                                   (unsigned)(8 * sizeof(T)), h->stream));
+  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
+  HIPCHK(rocprim::radix_sort_pairs(tmp.p, tb, lb.as<T>(), lb2.as<T>(), R.idx.as<i64>(), idx2.as<i64>(), (size_t)k, 0u,
+                                   (unsigned)(8 * sizeof(T)), h->stream));
+  pfd_seg_end(h, 2);
+  PFDCHK(give_list(h, lb2.p, (size_t)k * sizeof(T), lbs_out, memspace));
+  return give_idxs(h, idx2.as<i64>(), k, idx_dtype, idxs_out, memspace);
+}
+
+}  // namespace
+
+extern "C" int pfd_subbasins_streamorder(pfd_raster *h, int dtype, const void *strord, int64_t min_sto, int idx_dtype,
+                                         void *idxs_out, int64_t cap, int64_t *k_out, int32_t *map_out, int memspace) {
+  PFDCHK(check_common(h, "subbasins_streamorder", strord, idx_dtype, idxs_out, cap, k_out));
+  if (!map_out) {
+    pfd_set_error("subbasins_streamorder: NULL map_out");
+    return PFD_EINVAL;
+  }
+  switch (dtype) {
+    case PFD_U8: return streamorder_t<u8>(h, strord, min_sto, idx_dtype, idxs_out, cap, k_out, map_out, memspace);
+    case PFD_I32: return streamorder_t<i32>(h, strord, min_sto, idx_dtype, idxs_out, cap, k_out, map_out, memspace);
+    case PFD_U32: return streamorder_t<u32>(h, strord, min_sto, idx_dtype, idxs_out, cap, k_out, map_out, memspace);
+    case PFD_I64: return streamorder_t<i64>(h, strord, min_sto, idx_dtype, idxs_out, cap, k_out, map_out, memspace);
+    default:
+      pfd_set_error("subbasins_streamorder: stream order dtype code %d is not supported (uint8, int32, uint32, int64)", dtype);
+      return PFD_EUNSUPPORTED;
+  }
+}
+
+extern "C" int pfd_outflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dtype, void *idxs_out, int64_t cap,
+                                int64_t *k_out, int memspace) {
+  PFDCHK(check_common(h, "outflow_idxs", region, idx_dtype, idxs_out, cap, k_out));
+  InArg v;
+  PFDCHK(v.bind(region, (size_t)h->n, memspace, h->stream));
+  Outlets R;
+  PFDCHK((outlets_of<R_REGION, u8>(h, (const u8 *)v.dev, 0, false, R)));
+  *k_out = (i64)R.k;
+  if ((i64)R.k <= cap) PFDCHK(give_idxs(h, R.idx.as<i64>(), R.k, idx_dtype, idxs_out, memspace));
+  return PFD_OK;
+}
+
+extern "C" int pfd_basin_outlets(pfd_raster *h, int dtype, const void *regions, int idx_dtype, void *idxs_out, void *lbs_out,
+                                 int64_t cap, int64_t *k_out, int memspace) {
+  PFDCHK(check_common(h, "basin_outlets", regions, idx_dtype, idxs_out, cap, k_out));
+  if (cap > 0 && !lbs_out) {
+    pfd_set_error("basin_outlets: NULL lbs_out");
+    return PFD_EINVAL;
+  }
+  switch (dtype) {
+    case PFD_I32: return basin_outlets_t<i32>(h, regions, idx_dtype, idxs_out, lbs_out, cap, k_out, memspace);
+    case PFD_U32: return basin_outlets_t<u32>(h, regions, idx_dtype, idxs_out, lbs_out, cap, k_out, memspace);
+    case PFD_I64: return basin_outlets_t<i64>(h, regions, idx_dtype, idxs_out, lbs_out, cap, k_out, memspace);
+    case PFD_U64: return basin_outlets_t<u64>(h, regions, idx_dtype, idxs_out, lbs_out, cap, k_out, memspace);
+    default:
+      pfd_set_error("basin_outlets: label dtype code %d is not supported (int32, uint32, int64, uint64)", dtype);
+      return PFD_EUNSUPPORTED;
+  }
+}

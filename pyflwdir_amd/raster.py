@@ -11,6 +11,8 @@ Mirrors (names, argument meaning, return conventions, error messages):
 * ``fillnodata``                       reference pyflwdir/flwdir.py:360-392
 * ``stream_order``                     reference pyflwdir/flwdir.py:508-547
 * ``basins``                           reference pyflwdir/pyflwdir.py:564-599
+* ``subbasins_streamorder``            reference pyflwdir/pyflwdir.py:601-629
+* ``basin_outlets`` / ``outflow_idxs`` reference pyflwdir/pyflwdir.py:720-740, :820-835
 * ``hand``                             reference pyflwdir/pyflwdir.py:1485-1511
 * ``add_pits`` / ``order_cells``       reference pyflwdir/flwdir.py:231-279, pyflwdir/pyflwdir.py:299-315
 * ``_check_data`` / ``_check_idxs_xy`` reference pyflwdir/flwdir.py:782-811, pyflwdir/pyflwdir.py:1548-1566
@@ -844,6 +846,61 @@ class FlwdirRaster(object):
             return dist.basins_blocks(self._d8, nb, idxs64, ids).reshape(self.shape)
         return self._h.basins(idxs64, ids).reshape(self.shape)
 
+    # -- outlets derived from the network (csrc/outlets.hip: mark, list in sequence order, number, fill) ------------
+    def subbasins_streamorder(self, strord=None, mask=None, min_sto=-2):
+        """Sub-basin map (int32, IDs from one) and the linear indices of the sub-basin outlets, for the streams of at least
+        stream order ``min_sto`` (negative: counted down from the largest order in ``strord``); reference
+        pyflwdir/pyflwdir.py:601-629, basins.py:67-103.  An outlet is a cell with ``strord >= min_sto`` that is a pit or
+        drains to a cell of another order; outlets are numbered up- to downstream (reversed ``idxs_seq``) and the numbers
+        filled upstream on the device.  The sequence is the device's own (``idxs_seq``: breadth-first, rank-sorted for
+        NEXTXY rasters) at any raster size; beyond 2**32 - 2 cells a raster with cycles raises NotImplementedError, like
+        ``basins`` on one handle.
+
+        ``mask`` is shape-checked and then ignored, which is what the reference does under the interpreter: its test
+        ``mask[idx0] is False`` is never true for a numpy bool, so a mask has no effect there either."""
+        strord = self._check_data(strord, "strord")
+        self._check_data(mask, "mask", optional=True)
+        code = _ORDER_CODES.get(strord.dtype)
+        if code is None:
+            if strord.dtype.kind not in "iub" or strord.dtype == np.uint64:
+                raise NotImplementedError(f"subbasins_streamorder: stream order dtype {strord.dtype} is not supported on the "
+                                          "HIP path (supported: bool, int8 ... int64, uint8 ... uint32)")
+            strord = strord.astype(np.uint8 if strord.dtype.kind == "b" else np.int32)
+            code = _ORDER_CODES[strord.dtype]
+        min_sto = int(min_sto)
+        if min_sto < 0:  # (the largest order of ALL cells of the array, like the reference)
+            min_sto = int(strord.max()) + min_sto
+        subbas, idxs_out = self._h.subbasins_streamorder(np.ascontiguousarray(strord), code, min_sto, self._idx_dtype)
+        return subbas.reshape(self.shape), idxs_out
+
+    def outflow_idxs(self, region):
+        """Linear indices of the most downstream cells within ``region`` (True inside): the cells of the region that are a
+        pit or drain out of it and have no other such cell further down their flow path, in ``idxs_seq`` order; reference
+        pyflwdir/pyflwdir.py:820-835, core.py:501-514."""
+        region = self._check_data(region, "region")
+        if region.dtype.kind not in "iubf":
+            raise NotImplementedError(f"outflow_idxs: region dtype {region.dtype} is not supported on the HIP path")
+        return self._h.outflow_idxs(np.ascontiguousarray(region != 0).view(np.uint8), self._idx_dtype)
+
+    def basin_outlets(self, basins):
+        """(labels, linear index of the outlet cell per label) of a basin map with background zero: a cell with a label
+        > 0 that is a pit or drains to a cell of another label; reference pyflwdir/pyflwdir.py:720-740,
+        regions.py:129-163.  Labels come in ``basins.dtype``, sorted by label.  A label with several outlets (a region that
+        is not one connected sub-basin) lists them up- to downstream (reversed ``idxs_seq``) — the reference sorts with
+        an unstable ``np.argsort`` and leaves that order unspecified."""
+        basins = self._check_data(basins, "basins")
+        dt = basins.dtype
+        code = _LABEL_CODES.get(dt)
+        lanes = basins
+        if code is None:
+            if dt.kind not in "iub":
+                raise NotImplementedError(f"basin_outlets: label dtype {dt} is not supported on the HIP path "
+                                          "(supported: bool and the integer dtypes)")
+            lanes = basins.astype(np.int32)  # (narrow integers and bool: widened, every value in range)
+            code = _hip.PFD_I32
+        lbs, idxs_out = self._h.basin_outlets(np.ascontiguousarray(lanes), code, self._idx_dtype)
+        return lbs.astype(dt, copy=False), idxs_out
+
     def _row_slices(self):
         """For rasters beyond 32-bit cell indices: (r0, r1, a, e, handle) over row chunks — a PLAIN handle on the rows
         [a, e) = the chunk [r0, r1) plus one context row on every inner side.  What a cell-local export (downstream index,
@@ -1184,6 +1241,10 @@ def _payload_args(flat, nodata):
     return view, code, nd, 0.0, 1
 
 
+_ORDER_CODES = {np.dtype(np.uint8): _hip.PFD_U8, np.dtype(np.int32): _hip.PFD_I32, np.dtype(np.uint32): _hip.PFD_U32,
+                np.dtype(np.int64): _hip.PFD_I64}
+_LABEL_CODES = {np.dtype(np.int32): _hip.PFD_I32, np.dtype(np.uint32): _hip.PFD_U32, np.dtype(np.int64): _hip.PFD_I64,
+                np.dtype(np.uint64): _hip.PFD_U64}
 _FILL_CODES = {np.dtype(np.int8): _hip.PFD_I8, np.dtype(np.uint8): _hip.PFD_U8, np.dtype(np.int16): _hip.PFD_I16,
                np.dtype(np.uint16): _hip.PFD_U16, np.dtype(np.int32): _hip.PFD_I32, np.dtype(np.uint32): _hip.PFD_U32,
                np.dtype(np.int64): _hip.PFD_I64, np.dtype(np.uint64): _hip.PFD_U64, np.dtype(np.float32): _hip.PFD_F32,
