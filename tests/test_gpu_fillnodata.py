@@ -13,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fill_cases as FC  # noqa: E402
 from golden_util import GOLD, digest  # noqa: E402
+from serial_refs import _ref_down, _ref_up  # noqa: E402  (the reference's two serial loops, core.py:120-188)
 
 pytestmark = pytest.mark.gpu
 
@@ -63,34 +64,6 @@ def test_fillnodata_golden(gpu_lib, monkeypatch, engine):
                     if not ok:
                         bad.append(k)
     assert n == 504 and not bad, bad[:20]
-
-
-# ---- a restatement of the reference's two serial loops (core.py:120-188) --------------------------------------------
-def _ref_up(idxs_ds, seq, data, nodata):
-    out = data.copy()
-    for x in seq:
-        d = idxs_ds[x]
-        if out[x] == nodata and out[d] != nodata:
-            out[x] = out[d]
-    return out
-
-
-def _ref_down(idxs_ds, seq, data, nodata, how):
-    out = data.copy()
-    for x in seq[::-1]:
-        d = idxs_ds[x]
-        if d == x:
-            continue
-        if data[d] == nodata and out[x] != nodata:
-            if out[d] == nodata:
-                out[d] = out[x]
-            elif how == "max":
-                out[d] = max(out[x], out[d])
-            elif how == "min":
-                out[d] = min(out[x], out[d])
-            else:
-                out[d] += out[x]
-    return out
 
 
 _EXPECTED = {}  # (raster, case) -> the serial loops' result, shared by the engines

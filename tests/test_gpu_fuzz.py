@@ -3,8 +3,15 @@ full of short paths, cycles, flow off the raster and into nodata) at shapes arou
 supertile edges, every operation against the oracle.  Random codes are the adversarial regime for
 the tiled engines (cycles that cross tile borders, tiles without any exit, partial tiles) and for
 the fallbacks to the level engine."""
+import os
+import sys
+import warnings
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from serial_refs import _ref_down, _ref_outlets, _ref_streamorder, _ref_up  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +92,27 @@ def test_random_rasters(gpu_lib, oracle, seed):
                           O.stream_distance(idxs_ds, seq, shape[1], mask=mask, real_length=False))
     assert np.array_equal(flw.stream_distance(unit="m").ravel(),
                           O.stream_distance(idxs_ds, seq, shape[1], latlon=False, transform=tuple(flw.transform)[:6]))
+    # fillnodata and the outlet lists against the reference's serial loops (tests/serial_refs.py)
+    f32 = np.where(rng.random(n) < 0.3, np.float32(-9999), rng.integers(-8, 9, n).astype(np.float32) / 4)
+    i32 = np.where(rng.random(n) < 0.3, 0, rng.integers(-5, 1000, n)).astype(np.int32)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for data, nd, direction, how in ((f32, -9999.0, "up", "max"), (f32, -9999.0, "down", "sum"), (i32, 0, "down", "max")):
+            exp = _ref_up(idxs_ds, seq, data, nd) if direction == "up" else _ref_down(idxs_ds, seq, data, nd, how)
+            got = flw.fillnodata(data.reshape(shape), nd, direction=direction, how=how)
+            assert got.dtype == exp.dtype and got.shape == shape and got.tobytes() == exp.tobytes(), (direction, how)
+    dsl, sql = idxs_ds.tolist(), seq.tolist()
+    strord = flw.stream_order()
+    sub_o, out_o = _ref_streamorder(dsl, sql, strord.ravel().tolist(), -2)
+    sub, out = flw.subbasins_streamorder(strord=strord, min_sto=-2)
+    assert sub.dtype == np.int32 and np.array_equal(sub.ravel(), np.array(sub_o, np.int32))
+    assert out.dtype == idxs_ds.dtype and np.array_equal(out, np.array(out_o, idxs_ds.dtype))
+    bas = flw.basins()
+    lbs_o, out_o = _ref_outlets(dsl, sql, bas.ravel().tolist())
+    order = np.argsort(np.array(lbs_o, bas.dtype), kind="stable")
+    lbs, out = flw.basin_outlets(bas)
+    assert lbs.dtype == bas.dtype and np.array_equal(lbs, np.array(lbs_o, bas.dtype)[order])
+    assert out.dtype == idxs_ds.dtype and np.array_equal(out, np.array(out_o, idxs_ds.dtype)[order])
     if shape[0] >= 4:
         from pyflwdir_amd import dist
 

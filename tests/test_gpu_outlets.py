@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import outlet_cases as OC  # noqa: E402
 from golden_util import GOLD, digest  # noqa: E402
+from serial_refs import _ref_outflow, _ref_outlets, _ref_streamorder  # noqa: E402  (the three serial loops)
 
 pytestmark = pytest.mark.gpu
 
@@ -64,41 +65,6 @@ def test_outlets_golden(gpu_lib, monkeypatch, engine):
                 if not ok:
                     bad.append(f"{key}_{i}")
     assert n == 10 * (5 * 2 + 2 * 1 + 2 * 2) and not bad, bad[:20]
-
-
-# ---- a restatement of the reference's three serial loops (plain lists: several times faster than numpy scalars) ------
-def _ref_streamorder(ds, seq, strord, min_sto):
-    if min_sto < 0:
-        min_sto = max(strord) + min_sto
-    sub, idxs = [0] * len(ds), []
-    for x in seq[::-1]:
-        if strord[x] >= min_sto and (ds[x] == x or strord[ds[x]] != strord[x]):
-            idxs.append(x)
-            sub[x] = len(idxs)
-    for x in seq:  # (core.fillnodata_upstream)
-        if sub[x] == 0 and sub[ds[x]] != 0:
-            sub[x] = sub[ds[x]]
-    return sub, idxs
-
-
-def _ref_outflow(ds, seq, region):
-    mask, idxs = [True] * len(ds), []
-    for x in seq:
-        if mask[ds[x]] and region[x] and (ds[x] == x or not region[ds[x]]):
-            idxs.append(x)
-            mask[x] = False
-        else:
-            mask[x] = mask[ds[x]]
-    return idxs
-
-
-def _ref_outlets(ds, seq, regions):
-    lbs, idxs = [], []
-    for x in seq[::-1]:
-        if regions[x] > 0 and (ds[x] == x or regions[ds[x]] != regions[x]):
-            idxs.append(x)
-            lbs.append(regions[x])
-    return lbs, idxs
 
 
 LARGE = [((1200, 1000), 3, dict(tilt=1 << 26, white=2, nodata_pct=10)),
