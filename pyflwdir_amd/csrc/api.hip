@@ -900,57 +900,38 @@ __global__ void k_export_u32(const u32 *__restrict__ src, u64 m, IDX *__restrict
   for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (u64)gridDim.x * blockDim.x) out[i] = (IDX)src[i];
 }
 
-static size_t idx_size(int idx_dtype) {
-  switch (idx_dtype) {
-    case PFD_I32:
-    case PFD_U32:
-      return 4;
-    case PFD_I64:
-      return 8;
-    default:
-      return 0;
-  }
-}
-
 extern "C" int pfd_idxs_ds(pfd_raster *h, int idx_dtype, void *out, int memspace) {
   PFDCHK(pfd_check_handle(h));
   if (h->gen) return pfd_gen_idxs_ds(h, idx_dtype, out, memspace);
   PFDCHK(pfd_require_whole(h, "idxs_ds"));
-  const size_t es = idx_size(idx_dtype);
-  if (!es || !out) {
-    pfd_set_error("pfd_idxs_ds: bad index dtype %d or NULL out", idx_dtype);
+  if (!out) {
+    pfd_set_error("pfd_idxs_ds: NULL out");
     return PFD_EINVAL;
   }
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * es, memspace));
-  const u32 grid = cdiv_u32((u64)h->n, 256);
-  if (idx_dtype == PFD_I32)
-    k_export_idxs_ds<i32><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (i32 *)o.dev);
-  else if (idx_dtype == PFD_U32)
-    k_export_idxs_ds<u32><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (u32 *)o.dev);
-  else
-    k_export_idxs_ds<i64><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (i64 *)o.dev);
-  KCHK();
-  return o.finish(h->stream);
+  return pfd_dispatch_idx(idx_dtype, "pfd_idxs_ds", [&](auto itag) -> int {
+    typedef typename decltype(itag)::type I;
+    OutArg o;
+    PFDCHK(o.bind(out, (size_t)h->n * sizeof(I), memspace));
+    k_export_idxs_ds<I><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo, (I *)o.dev);
+    KCHK();
+    return o.finish(h->stream);
+  });
 }
 
 int pfd_export_u32(pfd_raster *h, const u32 *src, i64 m, int idx_dtype, void *out, int memspace) {
-  const size_t es = idx_size(idx_dtype);
-  if (!es || !out) {
-    pfd_set_error("index export: bad index dtype %d or NULL out", idx_dtype);
+  if (!out) {
+    pfd_set_error("index export: NULL out");
     return PFD_EINVAL;
   }
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)m * es, memspace));
-  if (m > 0) {
-    const u32 grid = (u32)std::min<u64>(cdiv_u32((u64)m, 256), 1u << 22);
-    if (idx_dtype == PFD_I32)
-      k_export_u32<i32><<<grid, 256, 0, h->stream>>>(src, (u64)m, (i32 *)o.dev);
-    else if (idx_dtype == PFD_U32)
-      k_export_u32<u32><<<grid, 256, 0, h->stream>>>(src, (u64)m, (u32 *)o.dev);
-    else
-      k_export_u32<i64><<<grid, 256, 0, h->stream>>>(src, (u64)m, (i64 *)o.dev);
-    KCHK();
-  }
-  return o.finish(h->stream);
+  return pfd_dispatch_idx(idx_dtype, "index export", [&](auto itag) -> int {
+    typedef typename decltype(itag)::type I;
+    OutArg o;
+    PFDCHK(o.bind(out, (size_t)m * sizeof(I), memspace));
+    if (m > 0) {
+      const u32 grid = (u32)std::min<u64>(cdiv_u32((u64)m, 256), 1u << 22);
+      k_export_u32<I><<<grid, 256, 0, h->stream>>>(src, (u64)m, (I *)o.dev);
+      KCHK();
+    }
+    return o.finish(h->stream);
+  });
 }

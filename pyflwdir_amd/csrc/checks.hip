@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "rules.h"
 
 __global__ void __launch_bounds__(256) k_verify_upa(const u8 *__restrict__ ncode, const i32 *__restrict__ upa, u32 nrow,
                                                     u32 ncol, unsigned long long *__restrict__ res) {
@@ -156,14 +157,11 @@ __global__ void __launch_bounds__(256) k_verify_hand(const u8 *__restrict__ ncod
       badmv += v != -9999.0;
       continue;
     }
-    double exp = 0.0;
-    if (drain[i] == 1) {
-      ++ndrain;
-    } else {
-      const size_t p = chk_down(i, ncol, code);
-      const E dz = elev[i] - elev[p];
-      exp = (p == i ? 0.0 : hand[p]) + (double)dz;
-    }
+    const bool is_drain = drain[i] == 1;
+    ndrain += is_drain;
+    const size_t p = chk_down(i, ncol, code);
+    const E dz = HandRule<E>::dz(elev[i], elev[p]);
+    const double exp = p == i ? HandRule<E>::root(is_drain, dz) : HandRule<E>::fold(is_drain, dz, hand[p]);
     bad += !(__double_as_longlong(exp) == __double_as_longlong(v) || (exp != exp && v != v));
   }
   const unsigned long long vals[4] = {bad, badmv, csum, ndrain};
@@ -230,7 +228,7 @@ extern "C" int pfd_verify_hand(pfd_raster *h, const uint8_t *drain, int elev_dty
   }
   InArg dr, el, ha;
   PFDCHK(dr.bind(drain, (size_t)h->n, memspace, h->stream));
-  PFDCHK(el.bind(elevtn, (size_t)h->n * (elev_dtype == PFD_F32 ? 4 : 8), memspace, h->stream));
+  PFDCHK(el.bind(elevtn, (size_t)h->n * pfd_payload_bytes(elev_dtype), memspace, h->stream));
   PFDCHK(ha.bind(hand, (size_t)h->n * sizeof(double), memspace, h->stream));
   DevBuf acc;
   PFDCHK(acc.alloc(4 * sizeof(unsigned long long)));

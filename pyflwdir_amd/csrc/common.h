@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pfd.h"
@@ -306,6 +307,47 @@ struct OutArg {
     return PFD_OK;
   }
 };
+
+// dtype codes of the C-ABI -> element types.  f is a generic lambda that receives a typed tag (`typename decltype(tag)::type`
+// is the element type) and returns a status; a code outside the set is PFD_EUNSUPPORTED, for every entry point alike.
+template <class T>
+struct PfdTag {
+  typedef T type;
+};
+static inline size_t pfd_payload_bytes(int dtype) {  // 0: not a payload code (int32 / int64 / float32 / float64)
+  return dtype == PFD_I32 || dtype == PFD_F32 ? 4 : (dtype == PFD_I64 || dtype == PFD_F64 ? 8 : 0);
+}
+static inline size_t pfd_idx_bytes(int idx_dtype) {  // 0: not an index code (int32 / uint32 / int64)
+  return idx_dtype == PFD_I32 || idx_dtype == PFD_U32 ? 4 : (idx_dtype == PFD_I64 ? 8 : 0);
+}
+// the nodata value of a payload of type T, from the (integer, floating) pair the C-ABI passes
+template <class T>
+static inline T pfd_nodata_as(int64_t nodata_i, double nodata_f) {
+  return std::is_floating_point<T>::value ? (T)nodata_f : (T)nodata_i;
+}
+template <class F>
+static int pfd_dispatch_payload(int dtype, const char *what, F f) {
+  switch (dtype) {
+    case PFD_I32: return f(PfdTag<i32>{});
+    case PFD_I64: return f(PfdTag<i64>{});
+    case PFD_F32: return f(PfdTag<float>{});
+    case PFD_F64: return f(PfdTag<double>{});
+    default:
+      pfd_set_error("%s: unsupported payload dtype code %d", what, dtype);
+      return PFD_EUNSUPPORTED;
+  }
+}
+template <class F>
+static int pfd_dispatch_idx(int idx_dtype, const char *what, F f) {
+  switch (idx_dtype) {
+    case PFD_I32: return f(PfdTag<i32>{});
+    case PFD_U32: return f(PfdTag<u32>{});
+    case PFD_I64: return f(PfdTag<i64>{});
+    default:
+      pfd_set_error("%s: unsupported index dtype code %d", what, idx_dtype);
+      return PFD_EUNSUPPORTED;
+  }
+}
 
 // internal entry points shared between translation units -----------------------------------------
 int pfd_check_handle(pfd_raster *h);       // + normalises a deferred handle

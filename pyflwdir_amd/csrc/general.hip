@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "fill.h"
+#include "rules.h"
 
 int pfd_export_u32(pfd_raster *h, const u32 *src, i64 m, int idx_dtype, void *out, int memspace);  // api.hip
 
@@ -179,7 +180,7 @@ extern "C" int pfd_raster_create_general(const void *idxs_ds, int idx_dtype, int
     return PFD_EINVAL;
   }
   *out = nullptr;
-  const size_t es = idx_dtype == PFD_I64 ? 8 : ((idx_dtype == PFD_I32 || idx_dtype == PFD_U32) ? 4 : 0);
+  const size_t es = pfd_idx_bytes(idx_dtype);
   if (!idxs_ds || nrow <= 0 || ncol <= 0 || !es || (unsigned __int128)nrow * (unsigned __int128)ncol > 4294967294ull) {
     pfd_set_error("pfd_raster_create_general: invalid arguments (shape %lld x %lld, index dtype code %d)", (long long)nrow,
                   (long long)ncol, idx_dtype);
@@ -201,12 +202,11 @@ extern "C" int pfd_raster_create_general(const void *idxs_ds, int idx_dtype, int
     }
     const u32 grid = cdiv_u32(n, 256);
     unsigned long long *cnt = (unsigned long long *)h->ctrl;
-    if (idx_dtype == PFD_I32)
-      k_gen_import<i32><<<grid, 256, 0, h->stream>>>((const i32 *)in.dev, n, g->ds, h->ncode, cnt);
-    else if (idx_dtype == PFD_U32)
-      k_gen_import<u32><<<grid, 256, 0, h->stream>>>((const u32 *)in.dev, n, g->ds, h->ncode, cnt);
-    else
-      k_gen_import<i64><<<grid, 256, 0, h->stream>>>((const i64 *)in.dev, n, g->ds, h->ncode, cnt);
+    (void)pfd_dispatch_idx(idx_dtype, "pfd_raster_create_general", [&](auto itag) -> int {  // (the code was checked above)
+      typedef typename decltype(itag)::type I;
+      k_gen_import<I><<<grid, 256, 0, h->stream>>>((const I *)in.dev, n, g->ds, h->ncode, cnt);
+      return PFD_OK;
+    });
     k_gen_check_targets<<<grid, 256, 0, h->stream>>>(g->ds, n, cnt);
     u64 c[4];
     if (hipMemcpyAsync(c, h->ctrl, sizeof(c), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
@@ -327,36 +327,29 @@ static int gen_levels(pfd_raster *h, bool up, const char *name, F launch) {
   return PFD_OK;
 }
 
-// ---- payload arithmetic (as in sweeps.hip) ---------------------------------------------------------------
-template <class T> struct GNum { static __device__ __forceinline__ T add(T a, T b) { return a + b; } };
-template <> struct GNum<i32> { static __device__ __forceinline__ i32 add(i32 a, i32 b) { return (i32)((u32)a + (u32)b); } };
-template <> struct GNum<i64> { static __device__ __forceinline__ i64 add(i64 a, i64 b) { return (i64)((u64)a + (u64)b); } };
-
+// ---- sweeps: plain CSR / ds[] traversal, the per-cell arithmetic of rules.h ---------------------------------------
 template <class T>
 __global__ void __launch_bounds__(256) k_gen_accu_up(const u32 *__restrict__ seq, u32 begin, u32 end,
                                                      const u32 *__restrict__ coff, const u32 *__restrict__ cidx,
-                                                     T *__restrict__ out, T nodata, int has_nodata) {
+                                                     T *__restrict__ out, AccuRule<T> r) {
   const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= end) return;
   const u32 x = seq[j];
   T acc = out[x];
   const u32 e0 = coff[x];
   for (u32 e = coff[x + 1]; e > e0; --e) {  // descending index: the order of the serial loop (streams.py:36-40)
-    const T a = out[cidx[e - 1]];
-    if (!has_nodata || (acc != nodata && a != nodata)) acc = GNum<T>::add(acc, a);
+    acc = r.join_br(acc, out[cidx[e - 1]]);
   }
   out[x] = acc;
 }
 template <class T>
 __global__ void __launch_bounds__(256) k_gen_accu_down(const u32 *__restrict__ seq, u32 begin, u32 end,
-                                                       const u32 *__restrict__ ds, T *__restrict__ out, T nodata,
-                                                       int has_nodata) {
+                                                       const u32 *__restrict__ ds, T *__restrict__ out, AccuRule<T> r) {
   const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= end) return;
   const u32 x = seq[j], p = ds[x];
-  if (p == x) return;
-  const T a = out[x], pv = out[p];
-  if (!has_nodata || (pv != nodata && a != nodata)) out[x] = GNum<T>::add(a, pv);
+  if (p == x) return;  // a pit keeps its own value
+  out[x] = r.join_br(out[x], out[p]);
 }
 __global__ void __launch_bounds__(256) k_gen_strahler(const u32 *__restrict__ seq, u32 begin, u32 end,
                                                       const u32 *__restrict__ coff, const u32 *__restrict__ cidx,
@@ -368,18 +361,10 @@ __global__ void __launch_bounds__(256) k_gen_strahler(const u32 *__restrict__ se
   for (u32 e = coff[x]; e < coff[x + 1]; ++e) {
     const u32 c = cidx[e];
     if (mask != nullptr && !mask[c]) continue;
-    const u32 v = out[c];
-    if (v > m) {
-      m = v;
-      cnt = 1;
-    } else if (v == m) {
-      ++cnt;
-    }
+    StrahlerRule::join(out[c], m, cnt);
   }
-  u32 r;
-  if (cnt == 0) r = (mask == nullptr || mask[x]) ? 1u : 0u;
-  else r = cnt >= 2 ? m + 1 : m;
-  out[x] = (u8)r;
+  const u32 own = cnt == 0 && (mask == nullptr || mask[x]) ? 1u : 0u;  // (only a headwater looks at its own mask byte)
+  out[x] = (u8)StrahlerRule::finish(m, cnt, own);
 }
 template <class L>
 __global__ void __launch_bounds__(256) k_gen_labels(const u32 *__restrict__ seq, u32 begin, u32 end,
@@ -387,9 +372,9 @@ __global__ void __launch_bounds__(256) k_gen_labels(const u32 *__restrict__ seq,
   const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= end) return;
   const u32 x = seq[j], p = ds[x];
-  if (out[x] != 0 || p == x) return;
-  const L pv = out[p];
-  if (pv != 0) out[x] = pv;
+  if (p == x) return;  // a pit keeps its seed, or 0
+  const L v = LabelRule<L>::fold(out[x], out[p]);
+  if (v != 0) out[x] = v;
 }
 template <class E>
 __global__ void __launch_bounds__(256) k_gen_hand(const u32 *__restrict__ seq, u32 begin, u32 end, const u32 *__restrict__ ds,
@@ -398,12 +383,9 @@ __global__ void __launch_bounds__(256) k_gen_hand(const u32 *__restrict__ seq, u
   const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= end) return;
   const u32 x = seq[j], p = ds[x];
-  if (drain[x] == 1) {
-    out[x] = 0.0;
-    return;
-  }
-  const E dz = elev[x] - elev[p];
-  out[x] = (p == x ? 0.0 : out[p]) + (double)dz;
+  const bool is_drain = drain[x] == 1;
+  const E dz = HandRule<E>::dz(elev[x], elev[p]);
+  out[x] = p == x ? HandRule<E>::root(is_drain, dz) : HandRule<E>::fold(is_drain, dz, out[p]);
 }
 __global__ void __launch_bounds__(256) k_gen_dist(const u32 *__restrict__ seq, u32 begin, u32 end, const u32 *__restrict__ ds,
                                                   const u8 *__restrict__ mask, const float *__restrict__ steplen,
@@ -413,9 +395,9 @@ __global__ void __launch_bounds__(256) k_gen_dist(const u32 *__restrict__ seq, u
   const u32 x = seq[j], p = ds[x];
   const bool reset = p == x || (mask != nullptr && mask[x]);
   if (steplen != nullptr)
-    ((float *)out)[x] = reset ? 0.f : ((float *)out)[p] + steplen[x];
+    ((float *)out)[x] = DistRule<float>::fold(reset, true, steplen[x], ((float *)out)[p]);
   else
-    ((i32 *)out)[x] = reset ? 0 : (i32)((u32)((i32 *)out)[p] + 1u);
+    ((i32 *)out)[x] = DistRule<i32>::fold(reset, false, 1, ((i32 *)out)[p]);
 }
 __global__ void __launch_bounds__(256) k_gen_classic(const u32 *__restrict__ seq, u32 begin, u32 end, const u32 *__restrict__ ds,
                                                      const u8 *__restrict__ flag, const u8 *__restrict__ mask,
@@ -423,9 +405,8 @@ __global__ void __launch_bounds__(256) k_gen_classic(const u32 *__restrict__ seq
   const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= end) return;
   const u32 x = seq[j], p = ds[x];
-  u32 r = 0;
-  if (mask == nullptr || mask[x]) r = p == x ? 1u : (((u32)out[p] + flag[x]) & 0xFFu);
-  out[x] = (u8)r;
+  const bool outside = mask != nullptr && !mask[x];
+  out[x] = (u8)(p == x ? ClassicRule::root(outside) : ClassicRule::fold(outside, flag[x], out[p]));
 }
 __global__ void __launch_bounds__(256) k_gen_rank(const u32 *__restrict__ seq, u32 begin, u32 end, i32 level, i32 *__restrict__ out) {
   const u32 j = begin + blockIdx.x * blockDim.x + threadIdx.x;
@@ -525,15 +506,15 @@ __global__ void k_gen_add_pits(u32 *__restrict__ ds, u8 *__restrict__ ncode, con
 
 // ---- entry points (called from the C-ABI functions when the handle is a general graph) -------------------------
 int pfd_gen_idxs_ds(pfd_raster *h, int idx_dtype, void *out, int memspace) {
-  const size_t es = idx_dtype == PFD_I64 ? 8 : 4;
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * es, memspace));
-  const u32 n = h->geo.n, grid = cdiv_u32(n, 256);
-  if (idx_dtype == PFD_I32) k_gen_export_ds<i32><<<grid, 256, 0, h->stream>>>(G(h)->ds, n, (i32 *)o.dev);
-  else if (idx_dtype == PFD_U32) k_gen_export_ds<u32><<<grid, 256, 0, h->stream>>>(G(h)->ds, n, (u32 *)o.dev);
-  else k_gen_export_ds<i64><<<grid, 256, 0, h->stream>>>(G(h)->ds, n, (i64 *)o.dev);
-  KCHK();
-  return o.finish(h->stream);
+  return pfd_dispatch_idx(idx_dtype, "pfd_idxs_ds", [&](auto itag) -> int {
+    typedef typename decltype(itag)::type I;
+    OutArg o;
+    PFDCHK(o.bind(out, (size_t)h->n * sizeof(I), memspace));
+    const u32 n = h->geo.n;
+    k_gen_export_ds<I><<<cdiv_u32(n, 256), 256, 0, h->stream>>>(G(h)->ds, n, (I *)o.dev);
+    KCHK();
+    return o.finish(h->stream);
+  });
 }
 int pfd_gen_order(pfd_raster *h) { return gen_order(h); }
 // the ordered graph on the device, for callers that walk it themselves (outlets.hip): downstream links (0xFFFFFFFF =
@@ -634,11 +615,11 @@ static int gen_accuflux_t(pfd_raster *h, const void *data, bool by_row, T nodata
   GenGraph *g = G(h);
   if (direction == PFD_UP) {
     PFDCHK(gen_levels(h, true, "general_accuflux_up", [&](u32 b, u32 e, i64) {
-      k_gen_accu_up<T><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->coff, g->cidx, (T *)o.dev, nodata, has_nodata);
+      k_gen_accu_up<T><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->coff, g->cidx, (T *)o.dev, AccuRule<T>{nodata, has_nodata});
     }));
   } else {
     PFDCHK(gen_levels(h, false, "general_accuflux_down", [&](u32 b, u32 e, i64) {
-      k_gen_accu_down<T><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->ds, (T *)o.dev, nodata, has_nodata);
+      k_gen_accu_down<T><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->ds, (T *)o.dev, AccuRule<T>{nodata, has_nodata});
     }));
   }
   if (mask_invalid) k_gen_mask_invalid<T><<<cdiv_u32(n, 256), 256, 0, h->stream>>>(g->ds, n, (T *)o.dev, nodata);
@@ -647,15 +628,10 @@ static int gen_accuflux_t(pfd_raster *h, const void *data, bool by_row, T nodata
 }
 int pfd_gen_accuflux(pfd_raster *h, int dtype, const void *data, bool by_row, int64_t nodata_i, double nodata_f,
                      int has_nodata, int direction, int mask_invalid, void *out, int memspace) {
-  switch (dtype) {
-    case PFD_I32: return gen_accuflux_t<i32>(h, data, by_row, (i32)nodata_i, has_nodata, direction, mask_invalid, out, memspace);
-    case PFD_I64: return gen_accuflux_t<i64>(h, data, by_row, (i64)nodata_i, has_nodata, direction, mask_invalid, out, memspace);
-    case PFD_F32: return gen_accuflux_t<float>(h, data, by_row, (float)nodata_f, has_nodata, direction, mask_invalid, out, memspace);
-    case PFD_F64: return gen_accuflux_t<double>(h, data, by_row, nodata_f, has_nodata, direction, mask_invalid, out, memspace);
-    default:
-      pfd_set_error("pfd_accuflux: unsupported payload dtype code %d", dtype);
-      return PFD_EUNSUPPORTED;
-  }
+  return pfd_dispatch_payload(dtype, "pfd_accuflux", [&](auto tag) -> int {
+    typedef typename decltype(tag)::type T;
+    return gen_accuflux_t<T>(h, data, by_row, pfd_nodata_as<T>(nodata_i, nodata_f), has_nodata, direction, mask_invalid, out, memspace);
+  });
 }
 int pfd_gen_upstream_area_cell(pfd_raster *h, i32 *out, int memspace) {
   OutArg o;
@@ -665,7 +641,7 @@ int pfd_gen_upstream_area_cell(pfd_raster *h, i32 *out, int memspace) {
   k_gen_fill_valid<i32><<<cdiv_u32(n, 256), 256, 0, h->stream>>>(g->ds, n, (i32 *)o.dev, 1, -9999);
   // (nodata cells are never in seq and never upstream of a valid cell: their -9999 stays untouched)
   PFDCHK(gen_levels(h, true, "general_count_up", [&](u32 b, u32 e, i64) {
-    k_gen_accu_up<i32><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->coff, g->cidx, (i32 *)o.dev, -9999, 1);
+    k_gen_accu_up<i32><<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->coff, g->cidx, (i32 *)o.dev, AccuRule<i32>{-9999, 1});
   }));
   return o.finish(h->stream);
 }
@@ -704,7 +680,7 @@ int pfd_gen_basins(pfd_raster *h, const i64 *idx_dev, const void *ids_dev, u32 k
 int pfd_gen_hand(pfd_raster *h, const u8 *drain, int elev_dtype, const void *elevtn, double *out, int memspace) {
   InArg dr, el;
   PFDCHK(dr.bind(drain, (size_t)h->n, memspace, h->stream));
-  PFDCHK(el.bind(elevtn, (size_t)h->n * (elev_dtype == PFD_F32 ? 4 : 8), memspace, h->stream));
+  PFDCHK(el.bind(elevtn, (size_t)h->n * pfd_payload_bytes(elev_dtype), memspace, h->stream));
   OutArg o;
   PFDCHK(o.bind(out, (size_t)h->n * sizeof(double), memspace));
   k_gen_fill<double><<<cdiv_u32(h->geo.n, 256), 256, 0, h->stream>>>((double *)o.dev, h->geo.n, -9999.0);
@@ -734,53 +710,46 @@ int pfd_gen_stream_distance(pfd_raster *h, const u8 *mask, int real_length, cons
   }));
   return o.finish(h->stream);
 }
-template <class T>
-static int gen_main_upstream_t(pfd_raster *h, const void *upa, double upa_min, int idx_dtype, void *out) {
-  GenGraph *g = G(h);
-  const u32 n = h->geo.n, grid = cdiv_u32(n, 256);
-  if (idx_dtype == PFD_I32) k_gen_main_upstream<T, i32><<<grid, 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const T *)upa, (T)upa_min, n, (i32 *)out);
-  else if (idx_dtype == PFD_U32) k_gen_main_upstream<T, u32><<<grid, 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const T *)upa, (T)upa_min, n, (u32 *)out);
-  else k_gen_main_upstream<T, i64><<<grid, 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const T *)upa, (T)upa_min, n, (i64 *)out);
-  KCHK();
-  return PFD_OK;
-}
 int pfd_gen_main_upstream(pfd_raster *h, int dtype, const void *uparea, double upa_min, int idx_dtype, void *out, int memspace) {
-  PFDCHK(gen_build_csr(h));
-  const size_t es = idx_dtype == PFD_I64 ? 8 : 4, ps = (dtype == PFD_I32 || dtype == PFD_F32) ? 4 : 8;
-  InArg a;
-  PFDCHK(a.bind(uparea, (size_t)h->n * ps, memspace, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * es, memspace));
-  int rc;
-  switch (dtype) {
-    case PFD_I32: rc = gen_main_upstream_t<i32>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-    case PFD_I64: rc = gen_main_upstream_t<i64>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-    case PFD_F32: rc = gen_main_upstream_t<float>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-    default: rc = gen_main_upstream_t<double>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-  }
-  PFDCHK(rc);
-  return o.finish(h->stream);
+  return pfd_dispatch_payload(dtype, "pfd_main_upstream", [&](auto ptag) -> int {
+    return pfd_dispatch_idx(idx_dtype, "pfd_main_upstream", [&](auto itag) -> int {
+      typedef typename decltype(ptag)::type T;
+      typedef typename decltype(itag)::type I;
+      PFDCHK(gen_build_csr(h));
+      InArg a;
+      PFDCHK(a.bind(uparea, (size_t)h->n * sizeof(T), memspace, h->stream));
+      OutArg o;
+      PFDCHK(o.bind(out, (size_t)h->n * sizeof(I), memspace));
+      GenGraph *g = G(h);
+      const u32 n = h->geo.n;
+      k_gen_main_upstream<T, I><<<cdiv_u32(n, 256), 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const T *)a.dev, (T)upa_min, n,
+                                                                        (I *)o.dev);
+      KCHK();
+      return o.finish(h->stream);
+    });
+  });
 }
 int pfd_gen_classic(pfd_raster *h, int idx_dtype, const void *idxs_us_main, const u8 *mask, u8 *out, int memspace) {
-  PFDCHK(gen_build_csr(h));
-  const size_t es = idx_dtype == PFD_I64 ? 8 : 4;
-  InArg mu, m;
-  PFDCHK(mu.bind(idxs_us_main, (size_t)h->n * es, memspace, h->stream));
-  PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n, memspace));
-  DevBuf flag;
-  PFDCHK(flag.alloc((size_t)h->n));
-  HIPCHK(hipMemsetAsync(o.dev, 0, (size_t)h->n, h->stream));
-  GenGraph *g = G(h);
-  const u32 n = h->geo.n, grid = cdiv_u32(n, 256);
-  if (idx_dtype == PFD_I32) k_gen_trib_flag<i32><<<grid, 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const i32 *)mu.dev, (const u8 *)m.dev, n, flag.as<u8>());
-  else if (idx_dtype == PFD_U32) k_gen_trib_flag<u32><<<grid, 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const u32 *)mu.dev, (const u8 *)m.dev, n, flag.as<u8>());
-  else k_gen_trib_flag<i64><<<grid, 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const i64 *)mu.dev, (const u8 *)m.dev, n, flag.as<u8>());
-  PFDCHK(gen_levels(h, false, "general_classic_order", [&](u32 b, u32 e, i64) {
-    k_gen_classic<<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->ds, flag.as<u8>(), (const u8 *)m.dev, (u8 *)o.dev);
-  }));
-  return o.finish(h->stream);
+  return pfd_dispatch_idx(idx_dtype, "pfd_stream_order_classic", [&](auto itag) -> int {
+    typedef typename decltype(itag)::type I;
+    PFDCHK(gen_build_csr(h));
+    InArg mu, m;
+    PFDCHK(mu.bind(idxs_us_main, (size_t)h->n * sizeof(I), memspace, h->stream));
+    PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
+    OutArg o;
+    PFDCHK(o.bind(out, (size_t)h->n, memspace));
+    DevBuf flag;
+    PFDCHK(flag.alloc((size_t)h->n));
+    HIPCHK(hipMemsetAsync(o.dev, 0, (size_t)h->n, h->stream));
+    GenGraph *g = G(h);
+    const u32 n = h->geo.n;
+    k_gen_trib_flag<I><<<cdiv_u32(n, 256), 256, 0, h->stream>>>(g->ds, g->coff, g->cidx, (const I *)mu.dev, (const u8 *)m.dev, n,
+                                                               flag.as<u8>());
+    PFDCHK(gen_levels(h, false, "general_classic_order", [&](u32 b, u32 e, i64) {
+      k_gen_classic<<<cdiv_u32(e - b, 256), 256, 0, h->stream>>>(g->seq, b, e, g->ds, flag.as<u8>(), (const u8 *)m.dev, (u8 *)o.dev);
+    }));
+    return o.finish(h->stream);
+  });
 }
 int pfd_gen_add_pits(pfd_raster *h, const i64 *idxs, i64 k) {
   GenGraph *g = G(h);
@@ -828,22 +797,24 @@ extern "C" int pfd_set_idxs_seq(pfd_raster *h, int idx_dtype, const void *seq, i
   }
   if (!seq && n_seq == 0) return PFD_OK;  // "forget the installed order": the next operation orders breadth-first
   PFDCHK(gen_order(h));  // own breadth-first order: levels + the number of cells in the sequence
-  const size_t es = idx_dtype == PFD_I64 ? 8 : 4;
-  if (!seq || (idx_dtype != PFD_I32 && idx_dtype != PFD_U32 && idx_dtype != PFD_I64) || n_seq != h->n_seq) {
+  if (!seq || n_seq != h->n_seq) {
     pfd_set_error("pfd_set_idxs_seq: the sequence must hold the %lld cells that drain to a pit", (long long)h->n_seq);
     return PFD_EINVAL;
   }
   const u32 n = h->geo.n, m = (u32)n_seq;
   std::vector<u32> useq(m);
-  for (u32 j = 0; j < m; ++j) {
-    const i64 v = idx_dtype == PFD_I64 ? ((const i64 *)seq)[j] : (idx_dtype == PFD_I32 ? (i64)((const i32 *)seq)[j] : (i64)((const u32 *)seq)[j]);
-    if (v < 0 || v >= (i64)n) {
-      pfd_set_error("pfd_set_idxs_seq: index %lld outside the raster", (long long)v);
-      return PFD_EINVAL;
+  PFDCHK(pfd_dispatch_idx(idx_dtype, "pfd_set_idxs_seq", [&](auto itag) -> int {
+    typedef typename decltype(itag)::type I;
+    for (u32 j = 0; j < m; ++j) {
+      const i64 v = (i64)((const I *)seq)[j];
+      if (v < 0 || v >= (i64)n) {
+        pfd_set_error("pfd_set_idxs_seq: index %lld outside the raster", (long long)v);
+        return PFD_EINVAL;
+      }
+      useq[j] = (u32)v;
     }
-    useq[j] = (u32)v;
-  }
-  (void)es;
+    return PFD_OK;
+  }));
   DevBuf rank, bad;
   PFDCHK(rank.alloc((size_t)n * sizeof(i32)));
   PFDCHK(bad.alloc(sizeof(unsigned long long)));

@@ -215,8 +215,6 @@ static int outlets_of(pfd_raster *h, const T *v, i64 min_sto, bool reversed, Out
   return outlets_run<RULE, T>(h, DownD8{h->ncode, h->geo}, (const u32 *)oseq.p, (u64)h->n_seq, v, min_sto, reversed, R);
 }
 
-static size_t idx_bytes(int idx_dtype) { return idx_dtype == PFD_I64 ? 8 : (idx_dtype == PFD_I32 || idx_dtype == PFD_U32) ? 4 : 0; }
-
 // k values from HBM into the caller's list (a host list: counted as a download of the call)
 static int give_list(pfd_raster *h, const void *dev, size_t bytes, void *out, int memspace) {
   if (!bytes) return PFD_OK;
@@ -237,21 +235,27 @@ static int give_list(pfd_raster *h, const void *dev, size_t bytes, void *out, in
 static int give_idxs(pfd_raster *h, const i64 *idx, u64 k, int idx_dtype, void *out, int memspace) {
   if (!k) return PFD_OK;
   if (idx_dtype == PFD_I64) return give_list(h, idx, (size_t)k * 8, out, memspace);
-  DevBuf tmp;
-  PFDCHK(tmp.alloc((size_t)k * 4));
-  if (idx_dtype == PFD_I32) k_export_i64<i32><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(idx, k, tmp.as<i32>());
-  else k_export_i64<u32><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(idx, k, tmp.as<u32>());
-  KCHK();
-  return give_list(h, tmp.p, (size_t)k * 4, out, memspace);
+  return pfd_dispatch_idx(idx_dtype, "outlet indices", [&](auto itag) -> int {
+    typedef typename decltype(itag)::type I;
+    DevBuf tmp;
+    PFDCHK(tmp.alloc((size_t)k * sizeof(I)));
+    k_export_i64<I><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(idx, k, tmp.as<I>());
+    KCHK();
+    return give_list(h, tmp.p, (size_t)k * sizeof(I), out, memspace);
+  });
 }
 
 static int check_common(pfd_raster *h, const char *what, const void *data, int idx_dtype, const void *idxs_out, i64 cap,
                         const i64 *k_out) {
   PFDCHK(pfd_check_handle(h));
   PFDCHK(pfd_require_unblocked(h, what));
-  if (!data || !k_out || cap < 0 || (cap > 0 && !idxs_out) || !idx_bytes(idx_dtype)) {
-    pfd_set_error("%s: bad arguments (NULL pointer, cap=%lld, index dtype %d)", what, (long long)cap, idx_dtype);
+  if (!data || !k_out || cap < 0 || (cap > 0 && !idxs_out)) {
+    pfd_set_error("%s: bad arguments (NULL pointer, cap=%lld)", what, (long long)cap);
     return PFD_EINVAL;
+  }
+  if (!pfd_idx_bytes(idx_dtype)) {
+    pfd_set_error("%s: unsupported index dtype code %d", what, idx_dtype);
+    return PFD_EUNSUPPORTED;
   }
   if (h->n > 4294967294ll && idx_dtype != PFD_I64) {
     pfd_set_error("%s of a raster of %lld cells needs the int64 index dtype (PFD_I64)", what, (long long)h->n);

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "exact.h"
 #include "fill.h"
+#include "rules.h"
 
 // Every ordered cell carries one byte of pre-decoded graph next to its index (built once per
 // ordering by k_seq_aux): the mask of the neighbour slots that drain into it (up-sweeps) and its
@@ -310,28 +311,6 @@ static int run_down(pfd_raster *h, const Op &op, const char *name) {
   return PFD_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// payload arithmetic: integers wrap like numba's fixed-width ints, floats are plain IEEE adds
-// ---------------------------------------------------------------------------------------------
-template <class T> struct Num;
-// neutral(): x with add(x, y) == y bit for bit, for every y (-0.0 for floats: +0.0 would turn a -0.0 into +0.0)
-template <> struct Num<i32> {
-  static __device__ __forceinline__ i32 neutral() { return 0; }
-  static __device__ __forceinline__ i32 add(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
-};
-template <> struct Num<i64> {
-  static __device__ __forceinline__ i64 neutral() { return 0; }
-  static __device__ __forceinline__ i64 add(i64 a, i64 b) { return (i64)((u64)a + (u64)b); }
-};
-template <> struct Num<float> {
-  static __device__ __forceinline__ float neutral() { return -0.0f; }
-  static __device__ __forceinline__ float add(float a, float b) { return a + b; }
-};
-template <> struct Num<double> {
-  static __device__ __forceinline__ double neutral() { return -0.0; }
-  static __device__ __forceinline__ double add(double a, double b) { return a + b; }
-};
-
 // payload accessors: a full per-cell array, or one value per raster ROW (cell areas of a regular
 // grid depend on the row only — upstream_area(unit != "cell") then needs no n-element input at all)
 template <class T>
@@ -370,8 +349,7 @@ struct AccuUp {
   Geo g;
   D data;
   T *out;
-  T nodata;
-  int has_nodata;
+  AccuRule<T> r;
   __device__ __forceinline__ T leaf(u32 nb) const { return out[nb]; }
   template <class F>
   __device__ __forceinline__ T combine(u32 x, u32 kids, F child) const {
@@ -379,10 +357,7 @@ struct AccuUp {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {  // children in descending linear index: the serial loop's order
       const int k = PFD_SLOT_DESC[q];
-      if (kids & (1u << k)) {
-        const T a = child(nb_of(g, x, k), k);
-        if (!has_nodata || (acc != nodata && a != nodata)) acc = Num<T>::add(acc, a);
-      }
+      if (kids & (1u << k)) acc = r.join_br(acc, child(nb_of(g, x, k), k));
     }
     return acc;
   }
@@ -401,12 +376,9 @@ struct AccuUp {
 #pragma unroll
         for (int q2 = 0; q2 < 8; ++q2) {
           const int k2 = slot_desc(q2);
-          if (kk & (1u << k2)) {
-            const T b = W[win_idx(k, k2)];
-            if (!has_nodata || (a != nodata && b != nodata)) a = Num<T>::add(a, b);
-          }
+          if (kk & (1u << k2)) a = r.join_br(a, W[win_idx(k, k2)]);
         }
-        if (!has_nodata || (acc != nodata && a != nodata)) acc = Num<T>::add(acc, a);
+        acc = r.join_br(acc, a);
       }
     }
     return acc;
@@ -415,18 +387,13 @@ struct AccuUp {
   // ---- exact-order engine (exact_sweep.h) ----
   typedef T LV;
   typedef T Elem;
-  __device__ __forceinline__ T join(T acc, T a) const {  // (branch-free: runs on the serial critical path)
-    const T sum = Num<T>::add(acc, a);
-    const bool ok = !has_nodata || (acc != nodata && a != nodata);
-    return ok ? sum : acc;
-  }
-  __device__ __forceinline__ T tile_init(u32 x, bool nd) const { return (MASKINV && nd) ? nodata : data.at(x); }
+  __device__ __forceinline__ T tile_init(u32 x, bool nd) const { return (MASKINV && nd) ? r.nodata : data.at(x); }
   __device__ __forceinline__ T tile_combine(u32 l, u32 kids, const T *val) const {
     T acc = val[l];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int k = slot_desc(q);
-      if (kids & (1u << k)) acc = join(acc, val[(int)l + slot_dr(k) * XT + slot_dc(k)]);
+      if (kids & (1u << k)) acc = r.join(acc, val[(int)l + slot_dr(k) * XT + slot_dc(k)]);
     }
     return acc;
   }
@@ -436,7 +403,7 @@ struct AccuUp {
     data.load4(x0, v);
     if (MASKINV) {
 #pragma unroll
-      for (int b = 0; b < 4; ++b) v[b] = (nd & (1u << b)) ? nodata : v[b];
+      for (int b = 0; b < 4; ++b) v[b] = (nd & (1u << b)) ? r.nodata : v[b];
     }
   }
   __device__ __forceinline__ void tile_store4(u32 x0, const T (&v)[4]) const { __builtin_memcpy(out + x0, v, 4 * sizeof(T)); }
@@ -459,21 +426,21 @@ struct AccuUp {
     T acc = data.at(x);
 #pragma unroll
     for (int q = 0; q < 8; ++q)
-      if (m & (1u << slot_desc(q))) acc = join(acc, v[q]);
+      if (m & (1u << slot_desc(q))) acc = r.join(acc, v[q]);
     return acc;
   }
   __device__ __forceinline__ T pre_post(u32 child) const { return out[child]; }
   __device__ __forceinline__ T first(T e) const { return e; }
   // real slot: accumulator = the cell's own part, operand = the heavy upstream cell's value (the running
   // value); post slot: accumulator = the running value, operand = the light upstream cell
-  __device__ __forceinline__ T fold(T t, T e, bool post) const { return join(post ? t : e, post ? e : t); }
+  __device__ __forceinline__ T fold(T t, T e, bool post) const { return r.join(post ? t : e, post ? e : t); }
   // speculative form (exact_sweep.h): a plain add is the exact result whenever neither operand is the nodata value
   static constexpr bool FAST = true;
   static constexpr bool FAST_CONST = false;  // (fold_fast leaves the running value unchanged whatever the element)
   // gather + fold of the short chains in one kernel (k_xtrunk_prescan): the gather is the bound, the fold hides under it
   static constexpr bool FUSE_UP = true;
   static constexpr bool FAST_SHORT = true;  // (the lane-per-chain fold of the short chains speculates too)
-  __device__ __forceinline__ bool special(T t, T e) const { return has_nodata && ((t == nodata) | (e == nodata)); }
+  __device__ __forceinline__ bool special(T t, T e) const { return r.special(t, e); }
   __device__ __forceinline__ T fold_fast(T t, T e) const { return Num<T>::add(e, t); }
 };
 
@@ -484,13 +451,11 @@ struct AccuDown {
   Geo g;
   D data;
   T *out;
-  T nodata;
-  int has_nodata;
+  AccuRule<T> r;
   __device__ __forceinline__ T top(u32 p) const { return out[p]; }
-  __device__ __forceinline__ T apply(u32 x, u32, bool root, T pv) const {
-    T a = data.at(x);  // a pit keeps its own value
-    if (!root && (!has_nodata || (pv != nodata && a != nodata))) a = Num<T>::add(a, pv);
-    return a;
+  __device__ __forceinline__ T apply(u32 x, u32 code, bool root, T pv) const {
+    const T e = dpre(x, code);
+    return root ? droot(e) : dfold(e, pv);
   }
   __device__ __forceinline__ void store(u32 x, T v) const { out[x] = v; }
   // ---- exact-order engine ----
@@ -498,11 +463,8 @@ struct AccuDown {
   __device__ __forceinline__ T dnodata(u32 x) const { return data.at(x); }  // nodata cells keep their input value
   __device__ __forceinline__ void dstore4(u32 x0, const T (&v)[4]) const { __builtin_memcpy(out + x0, v, 4 * sizeof(T)); }
   __device__ __forceinline__ T dpre(u32 x, u32) const { return data.at(x); }
-  __device__ __forceinline__ T droot(T e) const { return e; }
-  __device__ __forceinline__ T dfold(T e, T pv) const {
-    if (!has_nodata || (pv != nodata && e != nodata)) e = Num<T>::add(e, pv);
-    return e;
-  }
+  __device__ __forceinline__ T droot(T e) const { return e; }  // a pit keeps its own value
+  __device__ __forceinline__ T dfold(T e, T pv) const { return r.join_br(e, pv); }
   // tile image of the element (exact_sweep.h, k_xtile_down): the element itself, no flag
   typedef DElem DTile;
   static constexpr bool DTILE_FLAG = false;
@@ -522,7 +484,7 @@ struct AccuDown {
   }
   static constexpr bool FAST = true;
   static constexpr bool FAST_CONST = false;  // (fold_fast leaves the running value unchanged whatever the element)
-  __device__ __forceinline__ bool dspecial(T e, T pv) const { return has_nodata && ((pv == nodata) | (e == nodata)); }
+  __device__ __forceinline__ bool dspecial(T e, T pv) const { return r.special(pv, e); }
   __device__ __forceinline__ T dfold_fast(T e, T pv) const { return Num<T>::add(e, pv); }
   __device__ __forceinline__ T dneutral() const { return Num<T>::neutral(); }  // dfold_fast(dneutral(), pv) == pv
 };
@@ -573,32 +535,16 @@ struct Strahler {
   const u8 *mask;  // may be null
   u8 *out;
   __device__ __forceinline__ u32 leaf(u32 nb) const { return out[nb]; }
+  __device__ __forceinline__ u32 inside(u32 x) const { return (mask == nullptr || mask[x]) ? 1u : 0u; }
   template <class F>
   __device__ __forceinline__ u32 combine(u32 x, u32 kids, F child) const {
     u32 m = 0, cnt = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const u32 nb = nb_of(g, x, k);
-      if ((kids & (1u << k)) && (mask == nullptr || mask[nb])) {
-        const u32 v = child(nb, k) & 0xFFu;  // uint8 like the stored values
-        if (v > m) {
-          m = v;
-          cnt = 1;
-        } else if (v == m) {
-          ++cnt;
-        }
-      }
+      if ((kids & (1u << k)) && inside(nb)) StrahlerRule::join(child(nb, k) & 0xFFu, m, cnt);  // uint8 like the stored values
     }
-    if (cnt == 0) return (mask == nullptr || mask[x]) ? 1u : 0u;
-    return cnt >= 2 ? m + 1 : m;
-  }
-  static __device__ __forceinline__ void join(u32 v, u32 &m, u32 &cnt) {
-    if (v > m) {
-      m = v;
-      cnt = 1;
-    } else if (v == m) {
-      ++cnt;
-    }
+    return StrahlerRule::finish(m, cnt, cnt == 0 ? inside(x) : 0u);  // (only a headwater looks at its own mask byte)
   }
   __device__ __forceinline__ u32 eval2(u32 x, u32 kids, u64 kids2) const {
     u8 W[25], M[25];
@@ -617,13 +563,11 @@ struct Strahler {
         u32 m2 = 0, cnt2 = 0;
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2)
-          if ((kk & (1u << k2)) && M[win_idx(k, k2)]) join(W[win_idx(k, k2)], m2, cnt2);
-        const u32 v = (cnt2 == 0 ? 1u : (cnt2 >= 2 ? m2 + 1 : m2)) & 0xFFu;  // the child is inside the mask
-        join(v, m, cnt);
+          if ((kk & (1u << k2)) && M[win_idx(k, k2)]) StrahlerRule::join(W[win_idx(k, k2)], m2, cnt2);
+        StrahlerRule::join(StrahlerRule::finish(m2, cnt2, 1u) & 0xFFu, m, cnt);  // the child is inside the mask
       }
     }
-    if (cnt == 0) return M[12] ? 1u : 0u;
-    return cnt >= 2 ? m + 1 : m;
+    return StrahlerRule::finish(m, cnt, M[12] ? 1u : 0u);
   }
   __device__ __forceinline__ void store(u32 x, u32 v) const { out[x] = (u8)v; }
   // ---- exact-order engine: the closed form is order-independent, so the light upstream cells of a
@@ -634,7 +578,7 @@ struct Strahler {
   typedef u32 Elem;
   __device__ __forceinline__ u8 tile_init(u32 x, bool nodata_cell) const {
     if (nodata_cell) return 0;
-    const u32 m = (mask == nullptr || mask[x]) ? 1u : 0u;
+    const u32 m = inside(x);
     return (u8)((m << 7) | m);  // a headwater: 1 inside the mask, 0 outside
   }
   __device__ __forceinline__ u8 tile_combine(u32 l, u32 kids, const u8 *val) const {
@@ -644,10 +588,10 @@ struct Strahler {
     for (int k = 0; k < 8; ++k) {
       if (kids & (1u << k)) {
         const u32 c = val[(int)l + slot_dr(k) * XT + slot_dc(k)];
-        if (c & 0x80u) join(c & 0x7Fu, m, cnt);
+        if (c & 0x80u) StrahlerRule::join(c & 0x7Fu, m, cnt);
       }
     }
-    const u32 r = cnt == 0 ? own : (cnt >= 2 ? m + 1 : m);
+    const u32 r = StrahlerRule::finish(m, cnt, own);
     return (u8)((own << 7) | (r & 0x7Fu));
   }
   __device__ __forceinline__ void tile_store(u32 x, u8 v) const { out[x] = v & 0x7Fu; }
@@ -678,14 +622,13 @@ struct Strahler {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const u32 nb = nb_of(g, x, k);
-      if ((kids & (1u << k)) && (u32)k != hs && (mask == nullptr || mask[nb])) join((u32)out[nb], m, cnt);
+      if ((kids & (1u << k)) && (u32)k != hs && inside(nb)) StrahlerRule::join((u32)out[nb], m, cnt);
     }
     u32 hin = 0;
-    if (hs < 8) hin = (mask == nullptr || mask[nb_of(g, x, (int)hs)]) ? 1u : 0u;
-    const u32 own = (mask == nullptr || mask[x]) ? 1u : 0u;
-    const u32 lt = cnt == 0 ? own : (cnt >= 2 ? m + 1 : m);  // the order without the heavy cell / with a lower one
+    if (hs < 8) hin = inside(nb_of(g, x, (int)hs));
+    const u32 lt = StrahlerRule::finish(m, cnt, inside(x));  // the order without the heavy cell / with a lower one
     if (!hin) return 255u | (lt << 8) | (lt << 16);
-    const u32 eq = cnt >= 1 ? m + 1 : m;
+    const u32 eq = StrahlerRule::finish(m, cnt + 1u, 0u);  // the heavy cell is one more holder of m
     return m | (eq << 8) | ((cnt == 0 ? m : lt) << 16);  // (cnt == 0: m = 0 and t < 0 never happens)
   }
   __device__ __forceinline__ u32 pre_post(u32) const { return 0u; }
@@ -719,8 +662,7 @@ struct Labels {
   // its final label: both values lead to the same result, the label is a pure function of the path.)
   __device__ __forceinline__ L apply(u32 x, u32, bool root, L pv) const {
     const L own = out[x];
-    if (own != 0) return own;
-    return root ? (L)0 : pv;
+    return root ? LabelRule<L>::root(own) : LabelRule<L>::fold(own, pv);
   }
   __device__ __forceinline__ void store(u32 x, L v) const {
     if (v != 0) out[x] = v;
@@ -743,15 +685,13 @@ struct Hand {
   __device__ __forceinline__ bool watched(u32 code, double v) const { return code != D8_HALO && v == -HUGE_VAL; }
   __device__ __forceinline__ double top(u32 p) const { return out[p]; }
   __device__ __forceinline__ double apply(u32 x, u32 code, bool root, double pv) const {
-    if (drain[x] == 1) return 0.0;
-    const u32 p = d8_down(g, x, code);
-    const E dz = elev[x] - elev[p];  // difference in the elevation dtype (dem.py:328)
-    return (root ? 0.0 : pv) + (double)dz;
+    const DElem e = dpre(x, code);
+    return root ? droot(e) : dfold(e, pv);
   }
   __device__ __forceinline__ void store(u32 x, double v) const { out[x] = v; }
   // ---- exact-order engine ----
   struct DElem {
-    E dz;  // the difference in the elevation dtype (dem.py:328); widened when it is added
+    E dz;  // the difference in the elevation dtype (HandRule::dz); widened when it is added
     u32 is_drain;
   };
   __device__ __forceinline__ double dnodata(u32) const { return -9999.0; }
@@ -759,7 +699,7 @@ struct Hand {
   __device__ __forceinline__ DElem dpre(u32 x, u32 code) const {
     DElem e;
     e.is_drain = drain[x] == 1 ? 1u : 0u;
-    e.dz = elev[x] - elev[d8_down(g, x, code)];
+    e.dz = HandRule<E>::dz(elev[x], elev[d8_down(g, x, code)]);
     return e;
   }
   // tile image (k_xtile_down): the difference alone, the drain flag goes to the tile's flag bitmap
@@ -784,23 +724,23 @@ struct Hand {
   }
   __device__ __forceinline__ double dtile4_get(const DQuad &q, int b, bool &is_drain) const {
     is_drain = ((q.d4 >> (8 * b)) & 0xFFu) == 1u;
-    return (double)(E)(q.ev[b] - q.dn[b]);
+    return HandRule<E>::dz(q.ev[b], q.dn[b]);
   }
   __device__ __forceinline__ double dtile(u32 x, u32 code, bool &is_drain) const {
     is_drain = drain[x] == 1;
-    return (double)(E)(elev[x] - elev[d8_down(g, x, code)]);
+    return HandRule<E>::dz(elev[x], elev[d8_down(g, x, code)]);
   }
-  __device__ __forceinline__ double dtroot(double dz, bool is_drain) const { return is_drain ? 0.0 : 0.0 + dz; }
-  __device__ __forceinline__ double dtfold(double dz, bool is_drain, double pv) const { return is_drain ? 0.0 : pv + dz; }
+  __device__ __forceinline__ double dtroot(double dz, bool is_drain) const { return HandRule<double>::root(is_drain, dz); }
+  __device__ __forceinline__ double dtfold(double dz, bool is_drain, double pv) const { return HandRule<double>::fold(is_drain, dz, pv); }
   __device__ __forceinline__ void top4(u32 x0, double (&v)[4]) const { __builtin_memcpy(v, out + x0, 32); }
   // speculative block fold (exact_sweep.h): a drain cell on a chain is rare; everything else is one add
   static constexpr bool FAST = true;
   static constexpr bool FAST_CONST = false;  // (fold_fast leaves the running value unchanged whatever the element)
   __device__ __forceinline__ bool dspecial(const DElem &e, double) const { return e.is_drain != 0u; }
-  __device__ __forceinline__ double dfold_fast(const DElem &e, double pv) const { return pv + (double)e.dz; }
+  __device__ __forceinline__ double dfold_fast(const DElem &e, double pv) const { return HandRule<E>::fold_fast(e.dz, pv); }
   __device__ __forceinline__ DElem dneutral() const { return DElem{(E)-0.0, 0u}; }  // pv + (-0.0) == pv for every pv
-  __device__ __forceinline__ double droot(const DElem &e) const { return e.is_drain ? 0.0 : 0.0 + (double)e.dz; }
-  __device__ __forceinline__ double dfold(const DElem &e, double pv) const { return e.is_drain ? 0.0 : pv + (double)e.dz; }
+  __device__ __forceinline__ double droot(const DElem &e) const { return HandRule<E>::root(e.is_drain != 0u, e.dz); }
+  __device__ __forceinline__ double dfold(const DElem &e, double pv) const { return HandRule<E>::fold(e.is_drain != 0u, e.dz, pv); }
 };
 
 // dem.floodplains (reference pyflwdir/dem.py:333-379): down- to upstream.  A stream cell (upstream area >=
@@ -1215,20 +1155,20 @@ static int accuflux_t(pfd_raster *h, const void *data, bool by_row, T nodata, in
   }
   if (direction == PFD_UP && by_row && mask_invalid && h->xplan_state == 1) {
     // upstream_area in area units: the tile pass of the exact-order engine masks the nodata cells itself
-    AccuUp<T, RowData<T>, true> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
+    AccuUp<T, RowData<T>, true> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, {nodata, has_nodata}};
     PFDCHK(run_exact_up(h, op, "exact_accuflux_up"));
     return o.finish(h->stream);
   } else if (direction == PFD_UP && by_row) {
-    AccuUp<T, RowData<T>> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
+    AccuUp<T, RowData<T>> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, {nodata, has_nodata}};
     PFDCHK(sweep_up(h, op, "sweep_accuflux_up", "exact_accuflux_up"));
   } else if (direction == PFD_UP) {
-    AccuUp<T> op{h->ncode, h->geo, CellData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
+    AccuUp<T> op{h->ncode, h->geo, CellData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, {nodata, has_nodata}};
     PFDCHK(sweep_up(h, op, "sweep_accuflux_up", "exact_accuflux_up"));
   } else if (by_row) {
-    AccuDown<T, RowData<T>> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
+    AccuDown<T, RowData<T>> op{h->ncode, h->geo, RowData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, {nodata, has_nodata}};
     PFDCHK(sweep_down(h, op, "sweep_accuflux_down", "exact_accuflux_down"));
   } else {
-    AccuDown<T> op{h->ncode, h->geo, CellData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, nodata, has_nodata};
+    AccuDown<T> op{h->ncode, h->geo, CellData<T>{(const T *)d.dev, h->geo}, (T *)o.dev, {nodata, has_nodata}};
     PFDCHK(sweep_down(h, op, "sweep_accuflux_down", "exact_accuflux_down"));
   }
   if (mask_invalid) {
@@ -1247,19 +1187,10 @@ static int accuflux_impl(pfd_raster *h, int dtype, const void *data, bool by_row
   }
   pfd_seg_clear(h);
   if (h->gen) return pfd_gen_accuflux(h, dtype, data, by_row, nodata_i, nodata_f, has_nodata, direction, mask_invalid, out, memspace);
-  switch (dtype) {
-    case PFD_I32:
-      return accuflux_t<i32>(h, data, by_row, (i32)nodata_i, has_nodata, direction, mask_invalid, out, memspace);
-    case PFD_I64:
-      return accuflux_t<i64>(h, data, by_row, (i64)nodata_i, has_nodata, direction, mask_invalid, out, memspace);
-    case PFD_F32:
-      return accuflux_t<float>(h, data, by_row, (float)nodata_f, has_nodata, direction, mask_invalid, out, memspace);
-    case PFD_F64:
-      return accuflux_t<double>(h, data, by_row, nodata_f, has_nodata, direction, mask_invalid, out, memspace);
-    default:
-      pfd_set_error("pfd_accuflux: unsupported payload dtype code %d", dtype);
-      return PFD_EUNSUPPORTED;
-  }
+  return pfd_dispatch_payload(dtype, "pfd_accuflux", [&](auto tag) -> int {
+    typedef typename decltype(tag)::type T;
+    return accuflux_t<T>(h, data, by_row, pfd_nodata_as<T>(nodata_i, nodata_f), has_nodata, direction, mask_invalid, out, memspace);
+  });
 }
 
 extern "C" int pfd_accuflux(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f,
@@ -1517,8 +1448,8 @@ __global__ void __launch_bounds__(256) k_hb_relax(const u8 *__restrict__ ncode, 
   const u32 p = d8_down(g, x, code);
   const double pv = __hip_atomic_load(&out[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (p == x || pv == -HUGE_VAL) return;  // (an unknown cell is never a root: roots are pits, drains or halo cells)
-  const E dz = elev[x] - elev[p];
-  __hip_atomic_store(&out[x], drain[x] == 1 ? 0.0 : pv + (double)dz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const E dz = HandRule<E>::dz(elev[x], elev[p]);
+  __hip_atomic_store(&out[x], HandRule<E>::fold(drain[x] == 1, dz, pv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (*changed == 0u) *changed = 1u;
 }
 
@@ -1545,8 +1476,7 @@ __global__ void __launch_bounds__(1024) k_hb_relax_wg(const u8 *__restrict__ nco
       xs[k] = x, ps[k] = p;
       if (p != x && __hip_atomic_load(&out[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == -HUGE_VAL) {
         open |= 1u << k;
-        const E d = elev[x] - elev[p];
-        dz[k] = (double)d;
+        dz[k] = HandRule<E>::dz(elev[x], elev[p]);  // (kept widened: the conversion is exact)
         isdrain |= drain[x] == 1 ? 1u << k : 0u;
       }
     }
@@ -1560,7 +1490,7 @@ __global__ void __launch_bounds__(1024) k_hb_relax_wg(const u8 *__restrict__ nco
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (((open >> k) & 1u) && pv[k] != -HUGE_VAL) {
-        __hip_atomic_store(&out[xs[k]], (isdrain >> k) & 1u ? 0.0 : pv[k] + dz[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&out[xs[k]], HandRule<double>::fold((isdrain >> k) & 1u, dz[k], pv[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         open &= ~(1u << k);
         moved = 1;
       }
@@ -1675,7 +1605,7 @@ extern "C" int pfd_hand_block(pfd_raster *h, const uint8_t *drain, int elev_dtyp
   PFDCHK(ensure_sweep_structure(h, true));
   InArg dr, el, sd;
   PFDCHK(dr.bind(drain, (size_t)h->n, memspace, h->stream));
-  PFDCHK(el.bind(elevtn, (size_t)h->n * (elev_dtype == PFD_F32 ? 4 : 8), memspace, h->stream));
+  PFDCHK(el.bind(elevtn, (size_t)h->n * pfd_payload_bytes(elev_dtype), memspace, h->stream));
   PFDCHK(sd.bind(halo_seed_host, 2 * (size_t)h->ncol * sizeof(double), h->block_seed_space, h->stream));
   OutArg o;
   PFDCHK(o.bind(out, (size_t)h->n * sizeof(double), memspace));
@@ -1987,10 +1917,10 @@ static int accuflux_block_t(pfd_raster *h, const void *data, bool by_row, T noda
   auto sweep = [&](auto data) -> int {  // (RowData: one value per device row, CellData: one per cell)
     typedef decltype(data) D;
     if (direction == PFD_DOWN) {
-      AccuDown<T, D> op{h->ncode, h->geo, data, o, nodata, has_nodata};
+      AccuDown<T, D> op{h->ncode, h->geo, data, o, {nodata, has_nodata}};
       return down_block_run<T>(op, f, "sweep_accuflux_down_block");
     }
-    AccuUp<T, D> op{h->ncode, h->geo, data, o, nodata, has_nodata};
+    AccuUp<T, D> op{h->ncode, h->geo, data, o, {nodata, has_nodata}};
     return up_block_run<T>(op, f, "sweep_accuflux_block");
   };
   PFDCHK(by_row ? sweep(RowData<T>{(const T *)d.dev, h->geo}) : sweep(CellData<T>{(const T *)d.dev, h->geo}));
@@ -2004,19 +1934,11 @@ extern "C" int pfd_accuflux_block(pfd_raster *h, int dtype, const void *data, in
     pfd_set_error("pfd_accuflux_block: bad arguments");
     return PFD_EINVAL;
   }
-  switch (dtype) {
-    case PFD_I32:
-      return accuflux_block_t<i32>(h, data, by_row != 0, (i32)nodata_i, has_nodata, direction, halo_seed_host, verify, out, memspace, boundary_rows_host, n_bad);
-    case PFD_I64:
-      return accuflux_block_t<i64>(h, data, by_row != 0, (i64)nodata_i, has_nodata, direction, halo_seed_host, verify, out, memspace, boundary_rows_host, n_bad);
-    case PFD_F32:
-      return accuflux_block_t<float>(h, data, by_row != 0, (float)nodata_f, has_nodata, direction, halo_seed_host, verify, out, memspace, boundary_rows_host, n_bad);
-    case PFD_F64:
-      return accuflux_block_t<double>(h, data, by_row != 0, nodata_f, has_nodata, direction, halo_seed_host, verify, out, memspace, boundary_rows_host, n_bad);
-    default:
-      pfd_set_error("pfd_accuflux_block: unsupported payload dtype code %d", dtype);
-      return PFD_EUNSUPPORTED;
-  }
+  return pfd_dispatch_payload(dtype, "pfd_accuflux_block", [&](auto tag) -> int {
+    typedef typename decltype(tag)::type T;
+    return accuflux_block_t<T>(h, data, by_row != 0, pfd_nodata_as<T>(nodata_i, nodata_f), has_nodata, direction, halo_seed_host,
+                               verify, out, memspace, boundary_rows_host, n_bad);
+  });
 }
 extern "C" int pfd_fillnodata_block(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f,
                                     int has_nodata, int direction, int how, const void *halo_seed_host, int verify,
@@ -2093,7 +2015,7 @@ extern "C" int pfd_hand(pfd_raster *h, const uint8_t *drain, int elev_dtype, con
   PFDCHK(ensure_sweep_structure(h));
   InArg dr, el;
   PFDCHK(dr.bind(drain, (size_t)h->n, memspace, h->stream));
-  PFDCHK(el.bind(elevtn, (size_t)h->n * (elev_dtype == PFD_F32 ? 4 : 8), memspace, h->stream));
+  PFDCHK(el.bind(elevtn, (size_t)h->n * pfd_payload_bytes(elev_dtype), memspace, h->stream));
   OutArg o;
   PFDCHK(o.bind(out, (size_t)h->n * sizeof(double), memspace));
   if (elev_dtype == PFD_F32)
@@ -2173,9 +2095,9 @@ struct Classic {
   const u8 *mask;  // may be null
   u8 *out;
   __device__ __forceinline__ u32 top(u32 p) const { return out[p]; }
-  __device__ __forceinline__ u32 apply(u32 x, u32, bool root, u32 pv) const {
-    if (mask != nullptr && !mask[x]) return 0;  // outside the mask: stays 0
-    return root ? 1u : ((pv + flag[x]) & 0xFFu);  // uint8 arithmetic like the reference
+  __device__ __forceinline__ u32 apply(u32 x, u32 code, bool root, u32 pv) const {
+    const u32 e = dpre(x, code);
+    return root ? droot(e) : dfold(e, pv);
   }
   __device__ __forceinline__ void store(u32 x, u32 v) const { out[x] = (u8)v; }
   // ---- exact-order engine: bit 0 = tributary flag, bit 1 = outside the mask ----
@@ -2204,8 +2126,8 @@ struct Classic {
   static constexpr bool FAST_CONST = false;  // (fold_fast leaves the running value unchanged whatever the element)
   __device__ __forceinline__ bool dspecial(u32, u32) const { return false; }
   __device__ __forceinline__ u32 dfold_fast(u32, u32 pv) const { return pv; }
-  __device__ __forceinline__ u32 droot(u32 e) const { return (e & 2u) ? 0u : 1u; }
-  __device__ __forceinline__ u32 dfold(u32 e, u32 pv) const { return (e & 2u) ? 0u : ((pv + (e & 1u)) & 0xFFu); }
+  __device__ __forceinline__ u32 droot(u32 e) const { return ClassicRule::root((e & 2u) != 0u); }
+  __device__ __forceinline__ u32 dfold(u32 e, u32 pv) const { return ClassicRule::fold((e & 2u) != 0u, e & 1u, pv); }
 };
 
 template <class T>
@@ -2218,15 +2140,8 @@ struct Dist {
   T *out;
   __device__ __forceinline__ T top(u32 p) const { return out[p]; }
   __device__ __forceinline__ T apply(u32 x, u32 code, bool root, T pv) const {
-    if (root || (mask != nullptr && mask[x])) return (T)0;
-    if (dtab != nullptr) {
-      const int k = d8_slot(code);
-      const int dr = d8_dr(k), dc = d8_dc(k);
-      const u32 s = 2u * geo_row(g, x) + (u32)dr;  // r0 + r1
-      const int kind = (dr != 0 && dc != 0) ? 2 : (dr != 0 ? 0 : 1);
-      return (T)((float)pv + dtab[3u * s + (u32)kind]);
-    }
-    return (T)((u32)pv + 1u);
+    const T e = dpre(x, code);
+    return root ? droot(e) : dfold(e, pv);
   }
   __device__ __forceinline__ void store(u32 x, T v) const { out[x] = v; }
   // ---- exact-order engine: the step length of the cell (1 in cell units), negative = the distance restarts ----
@@ -2238,7 +2153,7 @@ struct Dist {
     if (dtab != nullptr) {
       const int k = d8_slot(code);
       const int dr = d8_dr(k), dc = d8_dc(k);
-      const u32 s = 2u * geo_row(g, x) + (u32)dr;
+      const u32 s = 2u * geo_row(g, x) + (u32)dr;  // r0 + r1
       const int kind = (dr != 0 && dc != 0) ? 2 : (dr != 0 ? 0 : 1);
       return (T)dtab[3u * s + (u32)kind];
     }
@@ -2261,62 +2176,35 @@ struct Dist {
   __device__ __forceinline__ bool dspecial(T, T) const { return false; }
   __device__ __forceinline__ T dfold_fast(T, T pv) const { return pv; }
   __device__ __forceinline__ T droot(T) const { return (T)0; }
-  __device__ __forceinline__ T dfold(T e, T pv) const {
-    if (e < (T)0) return (T)0;
-    if (dtab != nullptr) return (T)((float)pv + (float)e);
-    return (T)((u32)pv + 1u);
-  }
+  __device__ __forceinline__ T dfold(T e, T pv) const { return DistRule<T>::fold(e < (T)0, dtab != nullptr, e, pv); }
 };
-
-template <class T, class I>
-static void launch_main_upstream(pfd_raster *h, const void *upa, double upa_min, void *out) {
-  k_main_upstream<T, I><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo, (const T *)upa, (T)upa_min,
-                                                                        (I *)out);
-}
-template <class T>
-static int main_upstream_t(pfd_raster *h, const void *upa, double upa_min, int idx_dtype, void *out) {
-  if (idx_dtype == PFD_I32)
-    launch_main_upstream<T, i32>(h, upa, upa_min, out);
-  else if (idx_dtype == PFD_U32)
-    launch_main_upstream<T, u32>(h, upa, upa_min, out);
-  else
-    launch_main_upstream<T, i64>(h, upa, upa_min, out);
-  KCHK();
-  return PFD_OK;
-}
-static size_t idx_bytes(int idx_dtype) {
-  return idx_dtype == PFD_I32 || idx_dtype == PFD_U32 ? 4 : (idx_dtype == PFD_I64 ? 8 : 0);
-}
-static size_t payload_bytes(int dtype) {
-  return dtype == PFD_I32 || dtype == PFD_F32 ? 4 : (dtype == PFD_I64 || dtype == PFD_F64 ? 8 : 0);
-}
 
 extern "C" int pfd_main_upstream(pfd_raster *h, int dtype, const void *uparea, double upa_min, int idx_dtype,
                                  void *out, int memspace) {
   PFDCHK(pfd_check_handle(h));
   if (h->gen) return pfd_gen_main_upstream(h, dtype, uparea, upa_min, idx_dtype, out, memspace);
   PFDCHK(pfd_require_whole(h, "pfd_main_upstream"));
-  const size_t es = idx_bytes(idx_dtype), ps = payload_bytes(dtype);
-  if (!uparea || !out || !es || !ps) {
-    pfd_set_error("pfd_main_upstream: bad arguments (dtype %d, index dtype %d)", dtype, idx_dtype);
+  if (!uparea || !out) {
+    pfd_set_error("pfd_main_upstream: bad arguments");
     return PFD_EINVAL;
   }
   pfd_seg_clear(h);
-  InArg a;
-  PFDCHK(a.bind(uparea, (size_t)h->n * ps, memspace, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * es, memspace));
-  pfd_seg_begin(h, "main_upstream");
-  int rc;
-  switch (dtype) {
-    case PFD_I32: rc = main_upstream_t<i32>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-    case PFD_I64: rc = main_upstream_t<i64>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-    case PFD_F32: rc = main_upstream_t<float>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-    default: rc = main_upstream_t<double>(h, a.dev, upa_min, idx_dtype, o.dev); break;
-  }
-  PFDCHK(rc);
-  pfd_seg_end(h, 1);
-  return o.finish(h->stream);
+  return pfd_dispatch_payload(dtype, "pfd_main_upstream", [&](auto ptag) -> int {
+    return pfd_dispatch_idx(idx_dtype, "pfd_main_upstream", [&](auto itag) -> int {
+      typedef typename decltype(ptag)::type T;
+      typedef typename decltype(itag)::type I;
+      InArg a;
+      PFDCHK(a.bind(uparea, (size_t)h->n * sizeof(T), memspace, h->stream));
+      OutArg o;
+      PFDCHK(o.bind(out, (size_t)h->n * sizeof(I), memspace));
+      pfd_seg_begin(h, "main_upstream");
+      k_main_upstream<T, I><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo, (const T *)a.dev, (T)upa_min,
+                                                                            (I *)o.dev);
+      KCHK();
+      pfd_seg_end(h, 1);
+      return o.finish(h->stream);
+    });
+  });
 }
 
 // arithmetics.upstream_sum (reference pyflwdir/arithmetics.py:147-169; Flwdir.upstream_sum flwdir.py:412-433): the sum of
@@ -2328,7 +2216,7 @@ extern "C" int pfd_main_upstream(pfd_raster *h, int dtype, const void *uparea, d
 // in ascending index with the cell itself between its W and E neighbour — the operand order of the serial loop.
 template <class T>
 __global__ void __launch_bounds__(256) k_upstream_sum(const u8 *__restrict__ ncode, Geo g, const T *__restrict__ data,
-                                                      T nodata, int has_nodata, T *__restrict__ out) {
+                                                      AccuRule<T> rule, T *__restrict__ out) {
   const u32 x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= g.n) return;
   const u32 cx = ncode[x];
@@ -2340,7 +2228,7 @@ __global__ void __launch_bounds__(256) k_upstream_sum(const u8 *__restrict__ nco
     if (q == 4) {
       if (d8_is_dir(cx)) {  // a pit points at itself, a nodata cell at nothing: no event
         const T dd = data[d8_down(g, x, cx)];
-        if (has_nodata && (dx == nodata || dd == nodata)) acc = nodata;
+        if (rule.special(dx, dd)) acc = rule.nodata;
       }
       continue;
     }
@@ -2351,7 +2239,7 @@ __global__ void __launch_bounds__(256) k_upstream_sum(const u8 *__restrict__ nco
     const u32 cn = ncode[nb];
     if (!d8_is_dir(cn) || d8_down(g, nb, cn) != x) continue;
     const T dn = data[nb];
-    if (!has_nodata || (dn != nodata && dx != nodata)) acc = Num<T>::add(acc, dn);
+    if (!rule.special(dn, dx)) acc = Num<T>::add(acc, dn);
   }
   out[x] = acc;
 }
@@ -2361,61 +2249,55 @@ extern "C" int pfd_upstream_sum(pfd_raster *h, int dtype, const void *data, int6
   PFDCHK(pfd_check_handle(h));
   PFDCHK(pfd_reject_general(h, "pfd_upstream_sum"));
   PFDCHK(pfd_require_whole(h, "pfd_upstream_sum"));
-  const size_t ps = payload_bytes(dtype);
-  if (!data || !out || !ps) {
-    pfd_set_error("pfd_upstream_sum: bad arguments (dtype %d)", dtype);
+  if (!data || !out) {
+    pfd_set_error("pfd_upstream_sum: bad arguments");
     return PFD_EINVAL;
   }
   pfd_seg_clear(h);
-  InArg a;
-  PFDCHK(a.bind(data, (size_t)h->n * ps, memspace, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n * ps, memspace));
-  pfd_seg_begin(h, "upstream_sum");
-  const u32 grid = cdiv_u32(h->geo.n, 256);
-  switch (dtype) {
-    case PFD_I32: k_upstream_sum<i32><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (const i32 *)a.dev, (i32)nodata_i, has_nodata, (i32 *)o.dev); break;
-    case PFD_I64: k_upstream_sum<i64><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (const i64 *)a.dev, (i64)nodata_i, has_nodata, (i64 *)o.dev); break;
-    case PFD_F32: k_upstream_sum<float><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (const float *)a.dev, (float)nodata_f, has_nodata, (float *)o.dev); break;
-    default: k_upstream_sum<double><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (const double *)a.dev, nodata_f, has_nodata, (double *)o.dev); break;
-  }
-  KCHK();
-  pfd_seg_end(h, 1);
-  return o.finish(h->stream);
+  return pfd_dispatch_payload(dtype, "pfd_upstream_sum", [&](auto tag) -> int {
+    typedef typename decltype(tag)::type T;
+    InArg a;
+    PFDCHK(a.bind(data, (size_t)h->n * sizeof(T), memspace, h->stream));
+    OutArg o;
+    PFDCHK(o.bind(out, (size_t)h->n * sizeof(T), memspace));
+    pfd_seg_begin(h, "upstream_sum");
+    k_upstream_sum<T><<<cdiv_u32(h->geo.n, 256), 256, 0, h->stream>>>(
+        h->ncode, h->geo, (const T *)a.dev, AccuRule<T>{pfd_nodata_as<T>(nodata_i, nodata_f), has_nodata}, (T *)o.dev);
+    KCHK();
+    pfd_seg_end(h, 1);
+    return o.finish(h->stream);
+  });
 }
 
 extern "C" int pfd_stream_order_classic(pfd_raster *h, int idx_dtype, const void *idxs_us_main, const uint8_t *mask,
                                         uint8_t *out, int memspace) {
   PFDCHK(pfd_check_handle(h));
-  const size_t es = idx_bytes(idx_dtype);
-  if (!idxs_us_main || !out || !es) {
-    pfd_set_error("pfd_stream_order_classic: bad arguments (index dtype %d)", idx_dtype);
+  if (!idxs_us_main || !out) {
+    pfd_set_error("pfd_stream_order_classic: bad arguments");
     return PFD_EINVAL;
   }
   pfd_seg_clear(h);
   if (h->gen) return pfd_gen_classic(h, idx_dtype, idxs_us_main, mask, out, memspace);
-  PFDCHK(ensure_sweep_structure(h));
-  InArg mu, m;
-  PFDCHK(mu.bind(idxs_us_main, (size_t)h->n * es, memspace, h->stream));
-  PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(out, (size_t)h->n, memspace));
-  DevBuf flag;
-  PFDCHK(flag.alloc((size_t)h->n));
-  pfd_seg_begin(h, "init");
-  if (h->xplan_state != 1) HIPCHK(hipMemsetAsync(o.dev, 0, (size_t)h->n, h->stream));
-  const u32 grid = cdiv_u32((u64)h->n, 256);
-  if (idx_dtype == PFD_I32)
-    k_trib_flag<i32><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (const i32 *)mu.dev, (const u8 *)m.dev, flag.as<u8>());
-  else if (idx_dtype == PFD_U32)
-    k_trib_flag<u32><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (const u32 *)mu.dev, (const u8 *)m.dev, flag.as<u8>());
-  else
-    k_trib_flag<i64><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, (const i64 *)mu.dev, (const u8 *)m.dev, flag.as<u8>());
-  KCHK();
-  pfd_seg_end(h, 2);
-  Classic op{h->ncode, h->geo, flag.as<u8>(), (const u8 *)m.dev, (u8 *)o.dev};
-  PFDCHK(sweep_down(h, op, "sweep_classic_order", "exact_classic_order"));
-  return o.finish(h->stream);  // (synchronises: `flag` may be released afterwards)
+  return pfd_dispatch_idx(idx_dtype, "pfd_stream_order_classic", [&](auto itag) -> int {
+    typedef typename decltype(itag)::type I;
+    PFDCHK(ensure_sweep_structure(h));
+    InArg mu, m;
+    PFDCHK(mu.bind(idxs_us_main, (size_t)h->n * sizeof(I), memspace, h->stream));
+    PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
+    OutArg o;
+    PFDCHK(o.bind(out, (size_t)h->n, memspace));
+    DevBuf flag;
+    PFDCHK(flag.alloc((size_t)h->n));
+    pfd_seg_begin(h, "init");
+    if (h->xplan_state != 1) HIPCHK(hipMemsetAsync(o.dev, 0, (size_t)h->n, h->stream));
+    k_trib_flag<I><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo, (const I *)mu.dev, (const u8 *)m.dev,
+                                                                   flag.as<u8>());
+    KCHK();
+    pfd_seg_end(h, 2);
+    Classic op{h->ncode, h->geo, flag.as<u8>(), (const u8 *)m.dev, (u8 *)o.dev};
+    PFDCHK(sweep_down(h, op, "sweep_classic_order", "exact_classic_order"));
+    return o.finish(h->stream);  // (synchronises: `flag` may be released afterwards)
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2466,9 +2348,8 @@ __global__ void __launch_bounds__(256) k_trib_flag_info(const u8 *__restrict__ n
 extern "C" int pfd_trib_info_block(pfd_raster *h, int dtype, const void *uparea, double upa_min, const uint8_t *mask,
                                    uint8_t *tinfo, int memspace) {
   PFDCHK(block_prepare(h, "pfd_trib_info_block"));
-  const size_t ps = payload_bytes(dtype);
-  if (!uparea || !tinfo || !ps) {
-    pfd_set_error("pfd_trib_info_block: bad arguments (dtype %d)", dtype);
+  if (!uparea || !tinfo) {
+    pfd_set_error("pfd_trib_info_block: bad arguments");
     return PFD_EINVAL;
   }
   const u8 *kids = nullptr;  // per cell: the neighbours draining into it, halo cells included
@@ -2478,22 +2359,20 @@ extern "C" int pfd_trib_info_block(pfd_raster *h, int dtype, const void *uparea,
     PFDCHK(pfd_ensure_seq_aux(h));
     kids = h->cell_kids;
   }
-  InArg a, m;
-  PFDCHK(a.bind(uparea, (size_t)h->n * ps, memspace, h->stream));
-  PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
-  OutArg o;
-  PFDCHK(o.bind(tinfo, (size_t)h->n, memspace));
-  const u32 grid = cdiv_u32((u64)h->n, 256);
-  pfd_seg_begin(h, "trib_info");
-  switch (dtype) {
-    case PFD_I32: k_trib_info<i32><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, kids, (const i32 *)a.dev, (i32)upa_min, (const u8 *)m.dev, (u8 *)o.dev); break;
-    case PFD_I64: k_trib_info<i64><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, kids, (const i64 *)a.dev, (i64)upa_min, (const u8 *)m.dev, (u8 *)o.dev); break;
-    case PFD_F32: k_trib_info<float><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, kids, (const float *)a.dev, (float)upa_min, (const u8 *)m.dev, (u8 *)o.dev); break;
-    default: k_trib_info<double><<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, kids, (const double *)a.dev, upa_min, (const u8 *)m.dev, (u8 *)o.dev); break;
-  }
-  KCHK();
-  pfd_seg_end(h, 1);
-  return o.finish(h->stream);
+  return pfd_dispatch_payload(dtype, "pfd_trib_info_block", [&](auto tag) -> int {
+    typedef typename decltype(tag)::type T;
+    InArg a, m;
+    PFDCHK(a.bind(uparea, (size_t)h->n * sizeof(T), memspace, h->stream));
+    PFDCHK(m.bind(mask, (size_t)h->n, memspace, h->stream));
+    OutArg o;
+    PFDCHK(o.bind(tinfo, (size_t)h->n, memspace));
+    pfd_seg_begin(h, "trib_info");
+    k_trib_info<T><<<cdiv_u32((u64)h->n, 256), 256, 0, h->stream>>>(h->ncode, h->geo, kids, (const T *)a.dev, (T)upa_min,
+                                                                   (const u8 *)m.dev, (u8 *)o.dev);
+    KCHK();
+    pfd_seg_end(h, 1);
+    return o.finish(h->stream);
+  });
 }
 extern "C" int pfd_stream_order_classic_block(pfd_raster *h, const uint8_t *tinfo, const uint8_t *mask,
                                               const uint8_t *halo_seed_host, int verify, uint8_t *out, int memspace,
@@ -2618,7 +2497,7 @@ extern "C" int pfd_floodplains(pfd_raster *h, int elev_dtype, const void *elevtn
   pfd_seg_clear(h);
   PFDCHK(ensure_sweep_structure(h));
   InArg el, sm, hh;
-  PFDCHK(el.bind(elevtn, (size_t)h->n * (elev_dtype == PFD_F32 ? 4 : 8), memspace, h->stream));
+  PFDCHK(el.bind(elevtn, (size_t)h->n * pfd_payload_bytes(elev_dtype), memspace, h->stream));
   PFDCHK(sm.bind(is_stream, (size_t)h->n, memspace, h->stream));
   PFDCHK(hh.bind(stream_h, (size_t)h->n * sizeof(float), memspace, h->stream));
   OutArg o;
@@ -2668,7 +2547,7 @@ extern "C" int pfd_floodplains_block(pfd_raster *h, int elev_dtype, const void *
     return PFD_EINVAL;
   }
   InArg el, sm, hh;
-  PFDCHK(el.bind(elevtn, (size_t)h->n * (elev_dtype == PFD_F32 ? 4 : 8), memspace, h->stream));
+  PFDCHK(el.bind(elevtn, (size_t)h->n * pfd_payload_bytes(elev_dtype), memspace, h->stream));
   PFDCHK(sm.bind(is_stream, (size_t)h->n, memspace, h->stream));
   PFDCHK(hh.bind(stream_h, (size_t)h->n * sizeof(float), memspace, h->stream));
   BlockFrame f{h, verify, boundary_rows_host, n_bad};

@@ -347,3 +347,32 @@ def test_refusals(gpu_lib):
     h = _hip.RasterHandle.general(ds, 16, 16)  # (the library is still usable)
     assert np.array_equal(h.idxs_ds(np.int32), ds)
     h.close()
+
+
+def test_invalid_dtype_codes(gpu_lib):
+    """A payload or index dtype code outside the C-ABI's set is PFD_EUNSUPPORTED (NotImplementedError) on every entry
+    point alike, general graphs and D8 rasters; the handle stays usable."""
+    import ctypes as C
+
+    from pyflwdir_amd import _hip
+
+    c = next(c for c in GG.CASES if c["shape"] == (16, 16) and c["family"] == "recursive")
+    ds = GG.build(c)
+    n = ds.size
+    d8 = np.full((16, 16), 4, np.uint8)  # every cell drains south; the last row leaves the raster: pits
+    w = np.ones(n, np.float32)
+    for h in (_hip.RasterHandle.general(ds, 16, 16), _hip.RasterHandle(d8, 16, 16)):
+        with pytest.raises(NotImplementedError, match="unsupported payload dtype code 99"):
+            h.accuflux(w, 99, has_nodata=0)
+        with pytest.raises(NotImplementedError, match="unsupported payload dtype code 99"):
+            h.main_upstream(w, 99, np.int32)
+        out = np.empty(n, np.int64)
+        with pytest.raises(NotImplementedError, match="unsupported index dtype code 99"):
+            _hip.check(_hip.lib().pfd_main_upstream(h._h, _hip.PFD_F32, _hip.ptr(w), C.c_double(0.0), 99, _hip.ptr(out),
+                                                    _hip.PFD_HOST))
+        # the handle is still usable
+        upa = h.accuflux(w, _hip.PFD_F32, has_nodata=0)
+        assert upa.min() == 1.0 and upa.sum() >= n
+        main = h.main_upstream(upa, _hip.PFD_F32, np.int32)
+        assert main.shape == (n,) and (main >= -1).all() and (main < n).all()
+        h.close()
