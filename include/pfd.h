@@ -478,6 +478,24 @@ int pfd_outflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dtype, void *
                      int memspace);
 int pfd_basin_outlets(pfd_raster *h, int dtype, const void *regions, int idx_dtype, void *idxs_out, void *lbs_out,
                       int64_t cap, int64_t *k_out, int memspace);
+/* ---- stream segments: from outlet lists to segment lists (csrc/streams.hip) ----------------------------------------
+ * pfd_streams — streams.streams (reference pyflwdir/streams.py:132-188; FlwdirRaster.streams pyflwdir.py:894-974) as a
+ *   CSR triple.  `mask` uint8 (!= 0: stream cell; NULL: every cell).  With nup = the upstream count inside the mask, a
+ *   segment starts at every cell of the sequence that lies in the mask and is not walked through by another segment
+ *   (nup != 1, or no upstream neighbour that a walk leaves), in REVERSED sequence order; it follows the downstream
+ *   links — through cells outside the mask as well — up to and including the first cell with nup > 1, or ends at a pit.
+ *   n_out[0] = K segments, n_out[1] = M indices; offsets_out: K + 1 int64 (segment j is idxs_out[offsets[j] ..
+ *   offsets[j + 1])), idxs_out: M cells of `idx_dtype` (PFD_I32 / PFD_U32 / PFD_I64), pit_out: K uint8, 1 where the
+ *   segment ended at a pit.  The lists are the UNSPLIT segments: the reference's `max_len` pieces and the `[p, p]` entry
+ *   it appends after a segment that ends at pit p are slices of this triple and left to the caller.
+ *   Conventions of pfd_outflow_idxs: n_out is always written; the three lists are written only when K <= cap_segs and
+ *   M <= cap_idxs (not an error otherwise: the caller repeats the call with room; a sizing call passes caps of 0 and
+ *   NULL lists); `memspace` covers the mask and all outputs.  On D8 handles and general idxs_ds handles (over their
+ *   installed order, if any); not on row-block handles; a raster beyond 2^32 - 2 cells (64-bit cell indices) returns
+ *   PFD_EUNSUPPORTED: a list of that many segments is beyond what a caller can hold. */
+int pfd_streams(pfd_raster *h, const uint8_t *mask /* nullable */, int idx_dtype, void *idxs_out, int64_t cap_idxs,
+                int64_t *offsets_out /* cap_segs + 1 */, uint8_t *pit_out, int64_t cap_segs,
+                int64_t n_out[2] /* K segments, M indices */, int memspace);
 /* dem.floodplains (reference pyflwdir/dem.py:333-379; FlwdirRaster.floodplains pyflwdir.py:1513-1545):
  * `is_stream` uint8 (1 where uparea >= upa_min), `stream_h` float32 (uparea ** b on those cells — evaluated by
  * the caller in the reference's dtype), elevtn PFD_F32 / PFD_F64; out int8: 1 floodplain, 0 not, -1 off the sequence. */

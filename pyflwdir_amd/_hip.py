@@ -47,6 +47,7 @@ SYMBOLS = [
     "pfd_stream_order_classic_block", "pfd_upstream_area_rows_fixed", "pfd_floodplains_block_flags",
     "pfd_fillnodata", "pfd_fillnodata_block",
     "pfd_subbasins_streamorder", "pfd_outflow_idxs", "pfd_basin_outlets",
+    "pfd_streams",
 ]
 
 _lib = None
@@ -114,6 +115,8 @@ def lib() -> C.CDLL:
         L.pfd_outflow_idxs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]
         L.pfd_basin_outlets.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                         C.POINTER(C.c_int64), C.c_int]
+        L.pfd_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.POINTER(C.c_int64), C.c_int]
         L.pfd_stream_distance_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.pfd_strahler_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -699,6 +702,32 @@ class RasterHandle:
             if k.value <= cap:
                 return lbs[:k.value].copy(), idxs[:k.value].copy()
             cap = int(k.value)
+
+    # -- stream segments (csrc/streams.hip) ------------------------------------------------------------------------
+    def streams(self, mask, idx_dtype, idxs_out=None, offsets_out=None, pit_out=None, cap_idxs=None, cap_segs=None,
+                memspace=PFD_HOST):
+        """The unsplit stream segments of pfd_streams as a CSR triple: (idxs[M] of ``idx_dtype``, offsets[K + 1] int64,
+        pit[K] uint8); ``mask`` uint8 or None.  PFD_HOST: a sizing call, then the fetch with room for exactly K and M.
+        PFD_DEVICE: ``mask`` and the three lists (``cap_idxs`` / ``cap_segs`` entries; None with caps of 0: a sizing
+        call) are DeviceBuffers; returns (K, M), the lists are written when they fit."""
+        n_out = (C.c_int64 * 2)()
+        code = IDX_CODE[np.dtype(idx_dtype)]
+        if memspace != PFD_HOST:
+            check(lib().pfd_streams(self._h, ptr(mask), code, ptr(idxs_out), int(cap_idxs or 0), ptr(offsets_out),
+                                    ptr(pit_out), int(cap_segs or 0), n_out, memspace))
+            return int(n_out[0]), int(n_out[1])
+        # a sizing call in device memory first: the lists have no useful upper bound short of the raster's size
+        dmask = None if mask is None else DeviceBuffer(mask.nbytes, self.device).upload(mask)
+        try:
+            check(lib().pfd_streams(self._h, ptr(dmask), code, None, 0, None, None, 0, n_out, PFD_DEVICE))
+        finally:
+            if dmask is not None:
+                dmask.free()
+        k, m = int(n_out[0]), int(n_out[1])
+        idxs, offsets, pit = np.empty(m, idx_dtype), np.zeros(k + 1, np.int64), np.empty(k, np.uint8)
+        if k:
+            check(lib().pfd_streams(self._h, ptr(mask), code, ptr(idxs), m, ptr(offsets), ptr(pit), k, n_out, PFD_HOST))
+        return idxs, offsets, pit
 
     def floodplains(self, elevtn, elev_code, is_stream, stream_h):
         out = np.empty(self.n, np.int8)

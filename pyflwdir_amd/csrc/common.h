@@ -387,6 +387,8 @@ int pfd_gen_accuflux(pfd_raster *h, int dtype, const void *data, bool by_row, in
                      int has_nodata, int direction, int mask_invalid, void *out, int memspace);
 int pfd_gen_fillnodata(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
                        int direction, int how, void *out, int memspace);
+int pfd_fillnodata_impl(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
+                        int direction, int how, void *out, int memspace, bool fresh_timing);  // sweeps.hip: pfd_fillnodata
 size_t pfd_fill_lane_bytes(int dtype);  // sweeps.hip: bytes of a fillnodata payload lane, 0 for an unknown code
 int pfd_gen_upstream_area_cell(pfd_raster *h, i32 *out, int memspace);
 int pfd_gen_strahler(pfd_raster *h, const u8 *mask, u8 *out, int memspace);

@@ -1221,8 +1221,9 @@ static int fill_check_args(const void *data, const void *out, int direction, int
   return PFD_OK;
 }
 
-extern "C" int pfd_fillnodata(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
-                              int direction, int how, void *out, int memspace) {
+// (fresh_timing = false: the fill is a step of another call — streams.hip — whose timing record goes on)
+int pfd_fillnodata_impl(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
+                        int direction, int how, void *out, int memspace, bool fresh_timing) {
   PFDCHK(pfd_check_handle(h));
   PFDCHK(fill_check_args(data, out, direction, how, "pfd_fillnodata"));
   const size_t lane = pfd_fill_lane_bytes(dtype);
@@ -1230,7 +1231,7 @@ extern "C" int pfd_fillnodata(pfd_raster *h, int dtype, const void *data, int64_
     pfd_set_error("pfd_fillnodata: unsupported payload dtype code %d", dtype);
     return PFD_EUNSUPPORTED;
   }
-  pfd_seg_clear(h);
+  if (fresh_timing) pfd_seg_clear(h);
   if (h->gen) return pfd_gen_fillnodata(h, dtype, data, nodata_i, nodata_f, has_nodata, direction, how, out, memspace);
   InArg d;
   PFDCHK(d.bind(data, (size_t)h->n * lane, memspace, h->stream));
@@ -1259,6 +1260,10 @@ extern "C" int pfd_fillnodata(pfd_raster *h, int dtype, const void *data, int64_
   };
   PFDCHK(fill_dispatch(dtype, direction == PFD_DOWN, nodata_i, nodata_f, has_nodata, how, "pfd_fillnodata", fdown, fup));
   return o.finish(h->stream);
+}
+extern "C" int pfd_fillnodata(pfd_raster *h, int dtype, const void *data, int64_t nodata_i, double nodata_f, int has_nodata,
+                              int direction, int how, void *out, int memspace) {
+  return pfd_fillnodata_impl(h, dtype, data, nodata_i, nodata_f, has_nodata, direction, how, out, memspace, true);
 }
 
 extern "C" int pfd_strahler(pfd_raster *h, const uint8_t *mask, uint8_t *out, int memspace) {

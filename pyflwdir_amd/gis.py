@@ -1,7 +1,7 @@
 """Host-side raster geometry helpers of the hot path (numpy, float64 like the reference).
 
-Only what ``FlwdirRaster.upstream_area(unit != "cell")`` and ``basins(xy=...)`` need is
-restated here; the function names and semantics follow the reference's
+Only what ``FlwdirRaster.upstream_area(unit != "cell")``, ``basins(xy=...)`` and the geo-features of
+``streams`` / ``vectorize`` (``features``, reference gis_utils.py:490-549) need is restated here; the function names and semantics follow the reference's
 ``pyflwdir/gis_utils.py`` (cell area: :379-412, coordinates: :191-338, :342-359) so that
 callers can switch without edits.  These are O(nrow + ncol) or O(k) host computations; the
 O(n) weight raster for unit != "cell" is a broadcast of one value per row.
@@ -19,7 +19,7 @@ AREA_FACTORS = {"m2": 1.0, "ha": 1e4, "km2": 1e6, "cell": 1}  # reference gis_ut
 IDENTITY = Affine(1.0, 0.0, 0.0, 0.0, -1.0, 0.0)  # N->S orientation, reference gis_utils.py:13
 
 __all__ = ["AREA_FACTORS", "IDENTITY", "affine_to_coords", "cellarea", "area_grid", "area_rows",
-           "reggrid_area", "reggrid_dx", "reggrid_dy", "xy", "rowcol", "idxs_to_coords", "coords_to_idxs"]
+           "reggrid_area", "reggrid_dx", "reggrid_dy", "xy", "rowcol", "idxs_to_coords", "coords_to_idxs", "features"]
 
 
 def _unit_factor(unit):
@@ -212,3 +212,41 @@ def coords_to_idxs(xs, ys, transform, shape, op=np.floor, precision=None):
     if np.any((r < 0) | (r >= shape[0]) | (c < 0) | (c >= shape[1])):
         raise IndexError("XY coordinates outside domain")
     return r * shape[1] + c
+
+
+def features(flowpaths, xs=None, ys=None, transform=None, shape=None, **kwargs):
+    """A LineString geo-feature per flow path (list of 1-D arrays of linear indices), to be parsed by e.g.
+    ``geopandas.GeoDataFrame.from_features``; reference gis_utils.py:490-549.  Coordinates are the cell centres of
+    ``transform`` / ``shape``, or sampled from the ``xs`` / ``ys`` maps; flow paths with fewer than 2 elements are
+    skipped; the properties are ``idx`` (first cell), ``idx_ds`` (last cell), ``pit`` (the last two elements are the same
+    cell) and one value per ``kwargs`` map, sampled at the first cell.  The coordinates are computed once for the
+    concatenated indices and sliced per feature."""
+    if xs is None or ys is None:
+        if transform is None or shape is None:
+            raise ValueError("transform and shape should be provided if xs and ys are None")
+        _size = shape[0] * shape[1]
+    else:
+        _size = xs.size
+    for key in kwargs:
+        if not isinstance(kwargs[key], np.ndarray) or kwargs[key].size != _size:
+            raise ValueError(f'Kwargs map "{key}" should be ndarrays of same size as coordinates')
+    paths = [idxs for idxs in flowpaths if len(idxs) >= 2]
+    if not paths:
+        return []
+    flat = np.concatenate([np.asarray(idxs) for idxs in paths])
+    if xs is None or ys is None:
+        xi, yi = idxs_to_coords(flat, transform, shape)
+    else:
+        xi, yi = xs[flat], ys[flat]
+    ends = np.cumsum([len(idxs) for idxs in paths]).tolist()
+    feats, a = [], 0
+    for idxs, b in zip(paths, ends):
+        idx0 = idxs[0]
+        props = {key: kwargs[key].flat[idx0] for key in kwargs}
+        feats.append({
+            "type": "Feature",
+            "geometry": {"type": "LineString", "coordinates": list(zip(xi[a:b], yi[a:b]))},
+            "properties": {"idx": idx0, "idx_ds": idxs[-1], "pit": idxs[-1] == idxs[-2], **props},
+        })
+        a = b
+    return feats

@@ -13,6 +13,7 @@ Mirrors (names, argument meaning, return conventions, error messages):
 * ``basins``                           reference pyflwdir/pyflwdir.py:564-599
 * ``subbasins_streamorder``            reference pyflwdir/pyflwdir.py:601-629
 * ``basin_outlets`` / ``outflow_idxs`` reference pyflwdir/pyflwdir.py:720-740, :820-835
+* ``vectorize`` / ``streams`` / ``geofeatures`` reference pyflwdir/pyflwdir.py:865-892, :894-974, :976-1009
 * ``hand``                             reference pyflwdir/pyflwdir.py:1485-1511
 * ``add_pits`` / ``order_cells``       reference pyflwdir/flwdir.py:231-279, pyflwdir/pyflwdir.py:299-315
 * ``_check_data`` / ``_check_idxs_xy`` reference pyflwdir/flwdir.py:782-811, pyflwdir/pyflwdir.py:1548-1566
@@ -900,6 +901,84 @@ class FlwdirRaster(object):
             code = _hip.PFD_I32
         lbs, idxs_out = self._h.basin_outlets(np.ascontiguousarray(lanes), code, self._idx_dtype)
         return lbs.astype(dt, copy=False), idxs_out
+
+    # -- stream segments (csrc/streams.hip: flags, list of starts in sequence order, two walks) ----------------------
+    def stream_segments(self, mask=None, max_len=0, as_list=True):
+        """Linear indices per stream segment: the result of the reference's ``streams.streams`` (pyflwdir/streams.py:
+        132-188), which ``streams`` turns into geo-features.  Not a method of the reference.
+
+        A segment starts at every cell of ``mask`` (default: every cell) that no other segment walks through, in up- to
+        downstream order (reversed ``idxs_seq``), and runs down to and including the next cell with more than one upstream
+        neighbour inside the mask, or to a pit.  Returns a list of 1-D arrays in the dtype of ``idxs_ds``: each segment,
+        cut into its ``max_len`` pieces (neighbouring pieces share one cell) when it is longer than ``max_len > 0``, and
+        after a segment that ends at a pit ``p`` the entry ``[p, p]``.  The arrays are views into one flat index array.
+        ``as_list=False`` returns what the device computes, unsplit: (idxs[M], int64 offsets[K + 1], uint8 pit[K])."""
+        mask = self._check_data(mask, "mask", optional=True)
+        if self._row_blocks_needed() > 1:
+            raise NotImplementedError("stream_segments: stream segments are limited to rasters of at most 2**32 - 2 cells")
+        m = None if mask is None else np.ascontiguousarray(mask != 0).view(np.uint8)
+        idxs, offsets, pit = self._h.streams(m, self._idx_dtype)
+        if not as_list:
+            return idxs, offsets, pit
+        nseg = pit.size
+        pit = pit != 0
+        l = np.diff(offsets)
+        k, n = np.ones(nseg, np.int64), l
+        if max_len > 0:  # streams.py:169-180; np.rint is Python's round on float64 (halves to even)
+            multi = l / max_len > 1.5
+            k = np.where(multi, np.rint(l / max_len), 1).astype(np.int64)
+            n = np.where(multi, np.rint(l / np.maximum(k, 1)), l).astype(np.int64)
+        seg = np.repeat(np.arange(nseg), k)
+        i = np.arange(seg.size) - np.repeat(np.cumsum(k) - k, k)
+        end = offsets[1:][seg]
+        a = np.minimum(offsets[:-1][seg] + i * n[seg], end)
+        b = np.where(i == k[seg] - 1, end, np.minimum(offsets[:-1][seg] + n[seg] * (i + 1) + 1, end))
+        entries = k + pit  # per segment: its pieces, then [p, p]
+        first = np.cumsum(entries) - entries
+        out = [None] * int(entries.sum())
+        for j, a0, b0 in zip((first[seg] + i).tolist(), a.tolist(), b.tolist()):
+            out[j] = idxs[a0:b0]
+        pits = np.repeat(idxs[offsets[1:][pit] - 1], 2).reshape(-1, 2)
+        for j, pp in zip((first + k)[pit].tolist(), pits):
+            out[j] = pp
+        return out
+
+    def streams(self, mask=None, min_sto=1, xs=None, ys=None, idxs_out=None, max_len=0, direction="up", **kwargs):
+        """Stream segments as LineString geo-features (for ``geopandas.GeoDataFrame.from_features``); reference
+        pyflwdir/pyflwdir.py:894-974.  The stream cells are those of ``mask`` or, without one and with ``min_sto > 1``,
+        the cells of at least that Strahler order (``strord`` key-word map, computed when missing, and added as a sampled
+        column); segments longer than ``max_len > 0`` cells are cut into pieces of about that length.  Further key-word
+        arguments are maps sampled at the first cell of each segment.  ``idxs_out`` (segments between given outlet cells:
+        the reference's ``subgrid.segment_indices``) is not available on the HIP path."""
+        if idxs_out is not None:
+            raise NotImplementedError("streams: idxs_out (subgrid.segment_indices) is not available on the HIP path")
+        if mask is not None:
+            mask = self._check_data(mask, "mask")
+        elif min_sto > 1:
+            strord = self._check_data(kwargs.get("strord"), "strord")
+            mask = strord >= min_sto
+            kwargs.update(strord=strord)  # add strord column
+        idxs = self.stream_segments(mask=mask, max_len=max_len)
+        return self.geofeatures(idxs, xs=xs, ys=ys, **kwargs)
+
+    def vectorize(self, mask=None, xs=None, ys=None, direction="down", **kwargs):
+        """Each flow direction as a LineString geo-feature: the (cell, next cell) pairs of ``core.flwdir_tuples``
+        (core.py:260-269) along ``idxs_ds`` (``direction="down"``) or ``idxs_us_main``, for the cells where ``mask`` is 1;
+        reference pyflwdir/pyflwdir.py:865-892.  A pit gives the pair ``[p, p]``."""
+        nxt = self.idxs_ds if direction == "down" else self.idxs_us_main
+        mask = self._check_data(mask, "mask", optional=True)
+        keep = nxt != self._mv
+        if mask is not None:
+            keep &= mask == 1
+        idx0 = np.flatnonzero(keep).astype(nxt.dtype)
+        return self.geofeatures(list(np.stack([idx0, nxt[idx0]], axis=1)), xs=xs, ys=ys, **kwargs)
+
+    def geofeatures(self, flowpaths, xs=None, ys=None, **kwargs):
+        """Geo-features of flow paths given as a list of arrays of linear indices; cell-centre coordinates of the
+        transform unless ``xs`` / ``ys`` maps are given; reference pyflwdir/pyflwdir.py:976-1009, ``gis.features``."""
+        return gis.features(flowpaths=flowpaths, xs=self._check_data(xs, "xs", optional=True),
+                            ys=self._check_data(ys, "ys", optional=True), transform=self.transform, shape=self.shape,
+                            **kwargs)
 
     def _row_slices(self):
         """For rasters beyond 32-bit cell indices: (r0, r1, a, e, handle) over row chunks — a PLAIN handle on the rows
