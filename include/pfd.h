@@ -478,6 +478,33 @@ int pfd_outflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dtype, void *
                      int memspace);
 int pfd_basin_outlets(pfd_raster *h, int dtype, const void *regions, int idx_dtype, void *idxs_out, void *lbs_out,
                       int64_t cap, int64_t *k_out, int memspace);
+/* ---- the rest of the BASINS section (csrc/basins_ext.hip) -----------------------------------------------------------
+ * Lists follow the conventions of pfd_outflow_idxs (cap, *k_out always written, the list only when it fits).
+ * pfd_interbasin_mask — basins.interbasin_mask (basins.py:25-64; FlwdirRaster.interbasin_mask pyflwdir.py:742-766):
+ *   `region` uint8 (!= 0 inside), `stream` uint8 or NULL; out: n uint8 (0 / 1).  A cell of the sequence is set iff it
+ *   lies in the region, the basin of its pit holds a stream cell (no `stream`: always) and no cell on its path down to
+ *   the pit lies outside the region while draining into it; a cell off the sequence keeps stream && region.
+ * pfd_inflow_idxs — core.inflow_idxs (core.py:485-497; FlwdirRaster.inflow_idxs pyflwdir.py:804-818): the cells outside
+ *   `region` that drain into it and whose flag — handed down from the child that comes first in the sequence — is
+ *   still set; REVERSED sequence order.
+ * pfd_basin_bounds — regions.region_slices (regions.py:57-82) of a label map of `dtype` (PFD_I32, PFD_U32, PFD_I64 or
+ *   PFD_U64): lbs_out = the k sorted unique labels > 0 (cap labels of `dtype`), bounds_out = 4 * k int64 as
+ *   [row_min[k], row_max[k], col_min[k], col_max[k]] (inclusive).  Needs no flow directions: any handle of the shape.
+ * pfd_subbasins_pfafstetter — basins.subbasins_pfafstetter (basins.py:106-191; FlwdirRaster.subbasins_pfafstetter
+ *   pyflwdir.py:631-663): `uparea` n values of `dtype` (PFD_I32 / PFD_I64 / PFD_F32 / PFD_F64) or NULL = the upstream
+ *   cell count; the stream mask is uparea >= upa_min; `idxs_us_main` n int64 (-1 = none) or NULL = the main upstream
+ *   cells by upstream cell count; `idxs_pit`: npits cells, always a HOST list; depth 1 .. 8.  map_out: n int32 codes;
+ *   idxs_out: the outlets in the reference's append order.  Both of the reference's np.argsort calls are STABLE sorts
+ *   on the negated key here (ties keep list order; the reference leaves them unspecified).  32-bit cell indices only:
+ *   beyond 2^32 - 2 cells PFD_EUNSUPPORTED (pfd_main_upstream / pfd_stream_order_classic have no one-handle form). */
+int pfd_interbasin_mask(pfd_raster *h, const uint8_t *region, const uint8_t *stream, uint8_t *out, int memspace);
+int pfd_inflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dtype, void *idxs_out, int64_t cap, int64_t *k_out,
+                    int memspace);
+int pfd_basin_bounds(pfd_raster *h, int dtype, const void *labels, void *lbs_out, int64_t *bounds_out, int64_t cap,
+                     int64_t *k_out, int memspace);
+int pfd_subbasins_pfafstetter(pfd_raster *h, int dtype, const void *uparea, double upa_min, int depth,
+                              const int64_t *idxs_us_main, const int64_t *idxs_pit, int64_t npits, int idx_dtype,
+                              void *idxs_out, int64_t cap, int64_t *k_out, int32_t *map_out, int memspace);
 /* ---- stream segments: from outlet lists to segment lists (csrc/streams.hip) ----------------------------------------
  * pfd_streams — streams.streams (reference pyflwdir/streams.py:132-188; FlwdirRaster.streams pyflwdir.py:894-974) as a
  *   CSR triple.  `mask` uint8 (!= 0: stream cell; NULL: every cell).  With nup = the upstream count inside the mask, a

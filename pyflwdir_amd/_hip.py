@@ -48,6 +48,7 @@ SYMBOLS = [
     "pfd_fillnodata", "pfd_fillnodata_block",
     "pfd_subbasins_streamorder", "pfd_outflow_idxs", "pfd_basin_outlets",
     "pfd_streams",
+    "pfd_interbasin_mask", "pfd_inflow_idxs", "pfd_basin_bounds", "pfd_subbasins_pfafstetter",
 ]
 
 _lib = None
@@ -117,6 +118,13 @@ def lib() -> C.CDLL:
                                         C.POINTER(C.c_int64), C.c_int]
         L.pfd_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.POINTER(C.c_int64), C.c_int]
+        L.pfd_interbasin_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.pfd_inflow_idxs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]
+        L.pfd_basin_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.POINTER(C.c_int64), C.c_int]
+        L.pfd_subbasins_pfafstetter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
+                                                C.c_int]
         L.pfd_stream_distance_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.pfd_strahler_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -701,6 +709,51 @@ class RasterHandle:
                                           ptr(lbs), cap, C.byref(k), PFD_HOST))
             if k.value <= cap:
                 return lbs[:k.value].copy(), idxs[:k.value].copy()
+            cap = int(k.value)
+
+    # -- the rest of the BASINS section (csrc/basins_ext.hip) ---------------------------------------------------------
+    def interbasin_mask(self, region, stream):
+        """uint8 mask[n] of pfd_interbasin_mask; ``region`` uint8, ``stream`` uint8 or None."""
+        out = np.empty(self.n, np.uint8)
+        check(lib().pfd_interbasin_mask(self._h, ptr(region), ptr(stream), ptr(out), PFD_HOST))
+        return out
+
+    def inflow_idxs(self, region, idx_dtype, cap=None):
+        """Inflow cells of a uint8 region mask in reversed sequence order (pfd_inflow_idxs)."""
+        k = C.c_int64(0)
+        cap = self._outlet_cap() if cap is None else int(cap)
+        while True:
+            idxs = np.empty(cap, idx_dtype)
+            check(lib().pfd_inflow_idxs(self._h, ptr(region), IDX_CODE[np.dtype(idx_dtype)], ptr(idxs), cap, C.byref(k),
+                                        PFD_HOST))
+            if k.value <= cap:
+                return idxs[:k.value].copy()
+            cap = int(k.value)
+
+    def basin_bounds(self, labels, dtype_code, cap=None):
+        """(sorted unique labels[k] > 0, int64 [4, k] = row_min, row_max, col_min, col_max) of pfd_basin_bounds."""
+        k = C.c_int64(0)
+        cap = 4096 if cap is None else int(cap)
+        while True:
+            lbs, bounds = np.empty(cap, labels.dtype), np.empty(4 * cap, np.int64)
+            check(lib().pfd_basin_bounds(self._h, int(dtype_code), ptr(labels), ptr(lbs), ptr(bounds), cap, C.byref(k), PFD_HOST))
+            if k.value <= cap:
+                return lbs[:k.value].copy(), bounds[:4 * k.value].reshape(4, k.value).copy()
+            cap = int(k.value)
+
+    def subbasins_pfafstetter(self, uparea, dtype_code, upa_min, depth, idxs_us_main, idxs_pit, idx_dtype, cap=None):
+        """(int32 map[n], outlet cells[k]) of pfd_subbasins_pfafstetter; ``uparea`` / ``idxs_us_main`` (int64) may be None."""
+        k = C.c_int64(0)
+        out = np.empty(self.n, np.int32)
+        idxs_pit = np.ascontiguousarray(idxs_pit, dtype=np.int64)
+        cap = idxs_pit.size + max(1 << 16, 16 * idxs_pit.size) if cap is None else int(cap)
+        while True:
+            idxs = np.empty(cap, idx_dtype)
+            check(lib().pfd_subbasins_pfafstetter(self._h, int(dtype_code), ptr(uparea), float(upa_min), int(depth),
+                                                  ptr(idxs_us_main), ptr(idxs_pit), idxs_pit.size, IDX_CODE[np.dtype(idx_dtype)],
+                                                  ptr(idxs), cap, C.byref(k), ptr(out), PFD_HOST))
+            if k.value <= cap:
+                return out, idxs[:k.value].copy()
             cap = int(k.value)
 
     # -- stream segments (csrc/streams.hip) ------------------------------------------------------------------------

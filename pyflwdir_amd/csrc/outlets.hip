@@ -23,8 +23,6 @@
 #include "common.h"
 #include "lists.h"
 
-int pfd_gen_graph_dev(pfd_raster *h, const u32 **ds, const u32 **seq);  // general.hip: orders the graph
-
 namespace {
 
 enum { R_STO = 0, R_REGION = 1, R_LABEL = 2 };
@@ -71,11 +69,6 @@ __global__ void __launch_bounds__(256) k_drop_shadowed(const D d, u64 n, const u
     if ((threadIdx.x & 63u) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
   }
 }
-struct IsMarked {
-  const u8 *mark;
-  template <class I>
-  __host__ __device__ bool operator()(const I &x) const { return mark[x] != 0; }
-};
 // the list as the reference appends it (reversed: the loops over seq[::-1]) in 64-bit indices, and its numbers 1..k
 template <class I>
 __global__ void __launch_bounds__(256) k_number(const I *__restrict__ sel, u64 k, bool reversed, i64 *__restrict__ idx,
@@ -90,38 +83,10 @@ __global__ void __launch_bounds__(256) k_gather(const i64 *__restrict__ idx, u64
   const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
   if (i < k) out[i] = v[idx[i]];
 }
-template <class O>
-__global__ void __launch_bounds__(256) k_export_i64(const i64 *__restrict__ idx, u64 k, O *__restrict__ out) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i < k) out[i] = (O)idx[i];
-}
-
-static inline u32 sweep_grid(u64 n) { return (u32)std::min<u64>((n + 255) / 256, 1u << 22); }
-
 struct Outlets {  // the numbered list on the device
   DevBuf idx, ids;  // k x i64 cells in the reference's list order, k x u32 numbers 1..k
   u64 k = 0;
 };
-
-static int read_count(pfd_raster *h, const unsigned long long *dev, u64 *out) {
-  unsigned long long v = 0;
-  HIPCHK(hipMemcpyAsync(&v, dev, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  *out = (u64)v;
-  return PFD_OK;
-}
-
-// compaction of the cells [0, n) / of the sequence by the mark; `out` has room for `room` entries (>= what is marked)
-template <class In, class Out>
-static int select_marked(pfd_raster *h, In in, u64 m, const u8 *mark, Out *out, unsigned long long *count_dev) {
-  size_t tb = 0;
-  HIPCHK(rocprim::select(nullptr, tb, in, out, count_dev, (size_t)m, IsMarked{mark}, h->stream));
-  DevBuf tmp;
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::select(tmp.p, tb, in, out, count_dev, (size_t)m, IsMarked{mark}, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (`tmp` is released on return)
-  return PFD_OK;
-}
 
 template <int RULE, class T, class D, class I>
 static int outlets_run(pfd_raster *h, const D &d, const I *seq, u64 m, const T *v, i64 min_sto, bool reversed, Outlets &R) {
@@ -190,19 +155,6 @@ static int outlets_of(pfd_raster *h, const T *v, i64 min_sto, bool reversed, Out
   DevBuf oseq;
   PFDCHK(pfd_exact_seq_dev(h, oseq));
   return outlets_run<RULE, T>(h, DownD8{h->ncode, h->geo}, (const u32 *)oseq.p, (u64)h->n_seq, v, min_sto, reversed, R);
-}
-
-static int give_idxs(pfd_raster *h, const i64 *idx, u64 k, int idx_dtype, void *out, int memspace) {
-  if (!k) return PFD_OK;
-  if (idx_dtype == PFD_I64) return give_list(h, idx, (size_t)k * 8, out, memspace);
-  return pfd_dispatch_idx(idx_dtype, "outlet indices", [&](auto itag) -> int {
-    typedef typename decltype(itag)::type I;
-    DevBuf tmp;
-    PFDCHK(tmp.alloc((size_t)k * sizeof(I)));
-    k_export_i64<I><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(idx, k, tmp.as<I>());
-    KCHK();
-    return give_list(h, tmp.p, (size_t)k * sizeof(I), out, memspace);
-  });
 }
 
 static int check_common(pfd_raster *h, const char *what, const void *data, int idx_dtype, const void *idxs_out, i64 cap,

@@ -29,8 +29,6 @@
 #include "common.h"
 #include "lists.h"
 
-int pfd_gen_graph_dev(pfd_raster *h, const u32 **ds, const u32 **seq);  // general.hip: orders the graph
-
 namespace {
 
 enum { F_W = 1, F_STOP = 2, F_START = 4 };

@@ -13,6 +13,8 @@ Mirrors (names, argument meaning, return conventions, error messages):
 * ``basins``                           reference pyflwdir/pyflwdir.py:564-599
 * ``subbasins_streamorder``            reference pyflwdir/pyflwdir.py:601-629
 * ``basin_outlets`` / ``outflow_idxs`` reference pyflwdir/pyflwdir.py:720-740, :820-835
+* ``subbasins_pfafstetter`` / ``basin_bounds`` / ``interbasin_mask`` / ``inflow_idxs``
+                                       reference pyflwdir/pyflwdir.py:631-663, :694-718, :742-766, :804-818
 * ``vectorize`` / ``streams`` / ``geofeatures`` reference pyflwdir/pyflwdir.py:865-892, :894-974, :976-1009
 * ``hand``                             reference pyflwdir/pyflwdir.py:1485-1511
 * ``add_pits`` / ``order_cells``       reference pyflwdir/flwdir.py:231-279, pyflwdir/pyflwdir.py:299-315
@@ -901,6 +903,100 @@ class FlwdirRaster(object):
             code = _hip.PFD_I32
         lbs, idxs_out = self._h.basin_outlets(np.ascontiguousarray(lanes), code, self._idx_dtype)
         return lbs.astype(dt, copy=False), idxs_out
+
+    # -- the rest of the BASINS section (csrc/basins_ext.hip: closed forms of four serial loops) ----------
+    def _region_u8(self, data, name, what, optional=False):
+        data = self._check_data(data, name, optional=optional)
+        if data is None:
+            return None
+        if data.dtype.kind not in "iubf":
+            raise NotImplementedError(f"{what}: {name} dtype {data.dtype} is not supported on the HIP path")
+        return np.ascontiguousarray(data != 0).view(np.uint8)
+
+    def interbasin_mask(self, region, stream=None):
+        """Most downstream contiguous area within ``region``: where a stream flows out of the region and in again, only
+        the part below the lowest entry stays True; with a ``stream`` mask also only the basins that hold a stream cell;
+        reference pyflwdir/pyflwdir.py:742-766, basins.py:25-64.  Two label fills on the device; cells that do not
+        reach a pit keep ``stream & region`` (``region`` without a stream mask), as in the reference's loops over
+        ``idxs_seq``."""
+        r = self._region_u8(region, "region", "interbasin_mask")
+        s = self._region_u8(stream, "stream", "interbasin_mask", optional=True)
+        return self._h.interbasin_mask(r, s).view(np.bool_).reshape(self.shape)
+
+    def inflow_idxs(self, region):
+        """Linear indices of the cells just outside ``region`` (True inside) through which a river enters it, up- to
+        downstream (reversed ``idxs_seq``); reference pyflwdir/pyflwdir.py:804-818, core.py:485-497.  Below a listed
+        cell the reference's flag is handed on by the upstream cell that comes first in ``idxs_seq``, so an entry
+        further down the same chain of first upstream cells is not listed again."""
+        return self._h.inflow_idxs(self._region_u8(region, "region", "inflow_idxs"), self._idx_dtype)
+
+    def basin_bounds(self, basins=None, **kwargs):
+        """(labels, bounding boxes [xmin, ymin, xmax, ymax] per label, total bounding box) of a basin map with background
+        zero, by default ``self.basins(**kwargs)``; reference pyflwdir/pyflwdir.py:694-718, regions.py:57-125.  The rows
+        and columns a label spans are reduced on the device; the coordinates are the reference's float64 arithmetic."""
+        basins = self._check_data(basins, "basins", flatten=False, **kwargs)
+        if basins.ndim != 2:
+            raise ValueError('The "regions" array should be two dimensional')
+        dt = basins.dtype
+        code = _LABEL_CODES.get(dt)
+        lanes = basins
+        if code is None:
+            if dt.kind not in "iub":
+                raise NotImplementedError(f"basin_bounds: label dtype {dt} is not supported on the HIP path "
+                                          "(supported: bool and the integer dtypes)")
+            lanes = basins.astype(np.int32)  # (narrow integers and bool: widened, every value in range)
+            code = _hip.PFD_I32
+        lbs, rc = self._h.basin_bounds(np.ascontiguousarray(lanes).ravel(), code)
+        if lbs.size == 0:
+            raise ValueError("No regions found in data")
+        lbs = lbs.astype(dt, copy=False)
+        rmin, rmax, cmin, cmax = rc
+        xres, yres = self.transform[0], self.transform[4]
+        lons, lats = gis.affine_to_coords(self.transform, self.shape)
+        # regions.py:110-122: the first and last coordinate of the slice, swapped where the axis runs backwards
+        xmin, xmax = (lons[cmax], lons[cmin]) if xres < 0 else (lons[cmin], lons[cmax])
+        ymin, ymax = (lats[rmax], lats[rmin]) if yres < 0 else (lats[rmin], lats[rmax])
+        dx, dy = np.abs(xres) / 2, np.abs(yres) / 2
+        bboxs = np.stack([xmin - dx, ymin - dy, xmax + dx, ymax + dy], axis=1)
+        total_bbox = np.hstack([bboxs[:, :2].min(axis=0), bboxs[:, 2:].max(axis=0)])
+        return lbs, bboxs, total_bbox
+
+    def subbasins_pfafstetter(self, depth=1, uparea=None, upa_min=0.0):
+        """Pfafstetter sub-basin map (int32 codes of ``depth`` digits) and the linear indices of the sub- and inter-basin
+        outlets in the reference's order; reference pyflwdir/pyflwdir.py:631-663, basins.py:106-191.  ``uparea`` defaults
+        to the upstream cell count; streams are the cells with ``uparea >= upa_min``; the main stems follow
+        ``idxs_us_main``.  Per basin and level the four tributaries with the largest ``uparea`` become sub-basins 2, 4,
+        6, 8 (down- to upstream), the main stem between them the inter-basins 1, 3, 5, 7, 9.
+
+        The reference picks and orders the tributaries with two ``np.argsort`` calls whose order among equal areas is
+        unspecified; here both are stable sorts on the negated area (equal areas keep ``idxs_seq`` order).
+        ``upa_min=None`` meets an unbound variable in the reference and raises ValueError here.  Limited to rasters of
+        at most 2**32 - 2 cells: the main upstream cell and the classic stream order have no one-handle form beyond."""
+        if upa_min is None:
+            raise ValueError("upa_min must be a number")
+        depth = int(depth)
+        if depth < 1 or depth > 8:
+            raise ValueError("depth must be between 1 and 8")
+        if self._row_blocks_needed() > 1:
+            raise NotImplementedError("subbasins_pfafstetter: pfd_main_upstream and pfd_stream_order_classic have no "
+                                      "one-handle form beyond 2**32 - 2 cells")
+        code, upa = _hip.PFD_I32, None
+        if uparea is not None:
+            upa = self._check_data(uparea, "uparea")
+            if upa.dtype not in _PAYLOAD:
+                if upa.dtype.kind not in "if":  # (unsigned: the reference negates the areas in their own dtype)
+                    raise NotImplementedError(f"subbasins_pfafstetter: uparea dtype {upa.dtype} is not supported on the "
+                                              "HIP path")
+                upa = upa.astype(np.float64 if upa.dtype.kind == "f" else np.int64)
+            upa = np.ascontiguousarray(upa)
+            code = _PAYLOAD[upa.dtype]
+        us = None
+        if "idxs_us_main" in self._cached:  # (the reference takes the cached main upstream cells, whatever area chose them)
+            cached = self._cached["idxs_us_main"]
+            us = cached.astype(np.int64)
+            us[cached == self._mv] = -1
+        subbas, idxs_out = self._h.subbasins_pfafstetter(upa, code, upa_min, depth, us, self.idxs_pit, self._idx_dtype)
+        return subbas.reshape(self.shape), idxs_out
 
     # -- stream segments (csrc/streams.hip: flags, list of starts in sequence order, two walks) ----------------------
     def stream_segments(self, mask=None, max_len=0, as_list=True):
