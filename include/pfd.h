@@ -523,6 +523,42 @@ int pfd_subbasins_pfafstetter(pfd_raster *h, int dtype, const void *uparea, doub
 int pfd_streams(pfd_raster *h, const uint8_t *mask /* nullable */, int idx_dtype, void *idxs_out, int64_t cap_idxs,
                 int64_t *offsets_out /* cap_segs + 1 */, uint8_t *pit_out, int64_t cap_segs,
                 int64_t n_out[2] /* K segments, M indices */, int memspace);
+/* ---- upscaling: a coarse network from a fine D8 raster (csrc/upscale.hip) ------------------------------------------------
+ * The data-parallel methods of the reference's upscale.py, on the eager D8 handle's decoded downstream links (a general
+ * idxs_ds handle, a row block and a raster beyond 2^32 - 2 cells return PFD_EUNSUPPORTED).  The coarse grid has
+ * ceil(nrow / cellsize) x ceil(ncol / cellsize) = n1 cells (the last row and column may be partial); cellsize >= 1.
+ * `method`: PFD_UPSCALE_DMM   upscale.dmm  = dmm_exitcell + dmm_nextidx                (upscale.py:66-111, :114-169)
+ *           PFD_UPSCALE_EAM   upscale.eam  = eam_repcell + eam_nextidx                 (upscale.py:243-287, :290-335)
+ *           PFD_UPSCALE_EAM_PLUS  upscale.eam_plus = ihu(niter=0) = eam_repcell + ihu_outlets + ihu_nextidx
+ *                                                                    (upscale.py:1308-1309, :381-434, :437-496)
+ * `uparea`: n values of uparea_dtype (PFD_I32 / PFD_F32 / PFD_F64), compared in that type.  The representative / exit cell
+ * of a coarse cell is the valid fine cell, a pit or inside the method's selector (the coarse cell's edge, cell_edge
+ * upscale.py:41-46; the effective area, effective_area :214-223), with the largest uparea > 0 — the SMALLEST fine index
+ * among equals (the reference's ascending scan with a strict >); a NaN never wins; none: the missing value.
+ * `effarea_host`: HOST, min(cellsize, nrow) x min(cellsize, ncol) bytes, != 0 where (ri, ci) = (row % cellsize,
+ * col % cellsize) lies in the effective area — evaluated by the caller in float64, the device takes no square root;
+ * may be NULL for PFD_UPSCALE_DMM.
+ * Outputs, n1 entries of idx_dtype (PFD_I32 / PFD_U32 / PFD_I64; -1 cast = missing): idxs_out_out the fine index of each
+ * coarse cell's exit (DMM) / representative (EAM) / outlet (EAM+) cell, idxs_ds_out the coarse downstream index.
+ * `memspace` covers uparea and both outputs.  Every walk along the fine links is capped at n steps: a fine raster with a
+ * cycle returns PFD_EINVAL where the reference's `while True` never returns; so does an EAM+ cell for which the reference
+ * would index with its missing value (no outlet within the 8 neighbours and no effective area on the way).
+ * pfd_upscale_outlets — subgrid.outlets (reference pyflwdir/subgrid.py:13-48; FlwdirRaster.ucat_outlets pyflwdir.py:
+ *   1125-1157): idxs_out_out alone (PFD_UPSCALE_DMM: dmm_exitcell; PFD_UPSCALE_EAM_PLUS: eam_repcell + ihu_outlets;
+ *   PFD_UPSCALE_EAM: the representative cells).
+ * pfd_upscale_error — upscale.upscale_error (upscale.py:1312-1363; FlwdirRaster.upscale_error pyflwdir.py:1093-1121) on
+ *   the FINE handle: `idxs_out` (fine outlet cells) and `idxs_ds_coarse` (coarse downstream indices), k entries of
+ *   idx_dtype each; out: k uint8 — 1 where the first outlet cell (or pit) downstream of a cell's outlet is the outlet
+ *   of its downstream coarse cell, 0 where not, 255 where either entry is missing.  An entry outside its raster: PFD_EINVAL. */
+#define PFD_UPSCALE_DMM 0
+#define PFD_UPSCALE_EAM 1
+#define PFD_UPSCALE_EAM_PLUS 2
+int pfd_upscale(pfd_raster *h, int method, int64_t cellsize, int uparea_dtype, const void *uparea,
+                const uint8_t *effarea_host, int idx_dtype, void *idxs_ds_out, void *idxs_out_out, int memspace);
+int pfd_upscale_outlets(pfd_raster *h, int method, int64_t cellsize, int uparea_dtype, const void *uparea,
+                        const uint8_t *effarea_host, int idx_dtype, void *idxs_out_out, int memspace);
+int pfd_upscale_error(pfd_raster *h, int idx_dtype, const void *idxs_out, const void *idxs_ds_coarse, int64_t k,
+                      uint8_t *out, int memspace);
 /* dem.floodplains (reference pyflwdir/dem.py:333-379; FlwdirRaster.floodplains pyflwdir.py:1513-1545):
  * `is_stream` uint8 (1 where uparea >= upa_min), `stream_h` float32 (uparea ** b on those cells — evaluated by
  * the caller in the reference's dtype), elevtn PFD_F32 / PFD_F64; out int8: 1 floodplain, 0 not, -1 off the sequence. */

@@ -22,6 +22,7 @@ PFD_UP, PFD_DOWN = 0, 1
 # fillnodata payload codes beyond the five above (narrow integers travel widened in int32 lanes) and merge rules
 PFD_U64, PFD_I8, PFD_U8, PFD_I16, PFD_U16 = 6, 7, 8, 9, 10
 PFD_FILL_MAX, PFD_FILL_MIN, PFD_FILL_SUM = 0, 1, 2
+UPSCALE_METHOD = {"dmm": 0, "eam": 1, "eam_plus": 2}  # PFD_UPSCALE_*
 
 IDX_CODE = {np.dtype(np.int32): PFD_I32, np.dtype(np.uint32): PFD_U32, np.dtype(np.int64): PFD_I64}
 
@@ -49,6 +50,7 @@ SYMBOLS = [
     "pfd_subbasins_streamorder", "pfd_outflow_idxs", "pfd_basin_outlets",
     "pfd_streams",
     "pfd_interbasin_mask", "pfd_inflow_idxs", "pfd_basin_bounds", "pfd_subbasins_pfafstetter",
+    "pfd_upscale", "pfd_upscale_outlets", "pfd_upscale_error",
 ]
 
 _lib = None
@@ -125,6 +127,11 @@ def lib() -> C.CDLL:
         L.pfd_subbasins_pfafstetter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
                                                 C.c_int]
+        L.pfd_upscale.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_int]
+        L.pfd_upscale_outlets.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_int]
+        L.pfd_upscale_error.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
         L.pfd_stream_distance_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.pfd_strahler_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -755,6 +762,31 @@ class RasterHandle:
             if k.value <= cap:
                 return out, idxs[:k.value].copy()
             cap = int(k.value)
+
+    # -- upscaling (csrc/upscale.hip) ------------------------------------------------------------------------------------
+    def upscale(self, method, cellsize, uparea, effarea, idx_dtype, outlets_only=False):
+        """(coarse idxs_ds[n1], fine idxs_out[n1]) of pfd_upscale, or idxs_out alone (pfd_upscale_outlets); ``method`` a key
+        of UPSCALE_METHOD, ``uparea`` int32 / float32 / float64, ``effarea`` the uint8 effective-area mask or None (dmm)."""
+        cellsize = int(cellsize)
+        n1 = -(-self.nrow // cellsize) * -(-self.ncol // cellsize)
+        code, icode = _PAYLOAD_CODE[uparea.dtype], IDX_CODE[np.dtype(idx_dtype)]
+        idxs_out = np.empty(n1, idx_dtype)
+        if outlets_only:
+            check(lib().pfd_upscale_outlets(self._h, UPSCALE_METHOD[method], cellsize, code, ptr(uparea), ptr(effarea), icode,
+                                            ptr(idxs_out), PFD_HOST))
+            return idxs_out
+        idxs_ds = np.empty(n1, idx_dtype)
+        check(lib().pfd_upscale(self._h, UPSCALE_METHOD[method], cellsize, code, ptr(uparea), ptr(effarea), icode, ptr(idxs_ds),
+                                ptr(idxs_out), PFD_HOST))
+        return idxs_ds, idxs_out
+
+    def upscale_error(self, idxs_out, idxs_ds_coarse):
+        """uint8[k] of pfd_upscale_error on the FINE handle: 1 connected, 0 not, 255 missing."""
+        assert idxs_out.dtype == idxs_ds_coarse.dtype and idxs_out.size == idxs_ds_coarse.size
+        out = np.empty(idxs_out.size, np.uint8)
+        check(lib().pfd_upscale_error(self._h, IDX_CODE[idxs_out.dtype], ptr(idxs_out), ptr(idxs_ds_coarse), idxs_out.size,
+                                      ptr(out), PFD_HOST))
+        return out
 
     # -- stream segments (csrc/streams.hip) ------------------------------------------------------------------------
     def streams(self, mask, idx_dtype, idxs_out=None, offsets_out=None, pit_out=None, cap_idxs=None, cap_segs=None,

@@ -1261,6 +1261,101 @@ class FlwdirRaster(object):
         ucat_are[owner] = acc[1:][owner]
         return ucat_map, ucat_are
 
+    # -- upscaling (csrc/upscale.hip: a per-coarse-cell arg-max and per-coarse-cell walks) ------------------
+    def _has_loop(self):
+        """``not isvalid`` without a rank raster on the host: the handle's cell order (kept on the device once built)
+        holds every valid cell iff each of them reaches a pit."""
+        self._h.order_cells()
+        return self._h.info()["n_seq"] != self._h.info(counts=True)["n_valid"]
+
+    def _upscale_inputs(self, what, cellsize, uparea):
+        """(cellsize, uparea lanes, effective-area mask) of an upscaling call, after the refusals that come before any
+        kernel: a fine raster of the general engine, beyond 32-bit cell indices, or with a cycle (the reference's walks
+        never return from one)."""
+        if self.ftype not in ["d8", "ldd"] or self._d8 is None:
+            raise ValueError("The upscale method only works for D8 or LDD flow directon data.")
+        cellsize = int(cellsize)
+        if cellsize < 1:
+            raise ValueError("cellsize should be a positive integer")
+        if self._row_blocks_needed() > 1:
+            raise NotImplementedError(f"{what}: the walks along the fine flow directions have no form beyond 2**32 - 2 cells")
+        if self._has_loop():
+            raise ValueError(f"{what}: the flow direction raster holds a loop; the walks to the next outlet would never end")
+        upa = self._check_data(uparea, "uparea")
+        dt = upa.dtype
+        if dt not in (np.int32, np.float32, np.float64):  # (widened where every value keeps its place in the order)
+            if dt.kind in "iub" and dt.itemsize < 4:
+                upa = upa.astype(np.int32)
+            elif dt == np.uint32 or dt == np.float16:
+                upa = upa.astype(np.float64)
+            else:
+                raise NotImplementedError(f"{what}: uparea dtype {dt} is not supported on the HIP path")
+        return cellsize, np.ascontiguousarray(upa), _effective_area_mask(cellsize, self.shape)
+
+    def upscale(self, scale_factor, method="ihu", uparea=None, **kwargs):
+        """Upscale the flow direction network to a lower resolution: ``(FlwdirRaster, idxs_out)`` with the fine outlet
+        cell of every coarse cell; reference pyflwdir/pyflwdir.py:1013-1091, upscale.py.  Methods on the device: the
+        double maximum method ``"dmm"``, the effective area method ``"eam"`` and ``"eam_plus"`` (the first pass of the
+        iterative hydrography upscaling, ``ihu`` with ``niter=0``).  ``"ihu"`` itself relocates outlets in a serial loop
+        whose every step depends on the one before: it is not implemented, and there is no CPU fallback."""
+        if self.ftype not in ["d8", "ldd"]:
+            raise ValueError("The upscale method only works for D8 or LDD flow directon data.")
+        methods = ["ihu", "eam_plus", "com2", "com", "eam", "dmm"]
+        method = str(method).lower()
+        if method not in methods:
+            methodstr = "', '".join(methods)
+            raise ValueError(f"Unknown method: {method}, select from: '{methodstr}'")
+        if "com" in method:
+            import warnings
+
+            method_new = {"com": "eam_plus", "com2": "ihu"}.get(method)
+            warnings.warn(f"{method} renamed to {method_new}.", DeprecationWarning)
+            method = method_new
+        if method == "ihu":
+            raise NotImplementedError('upscale: the iterative method "ihu" is not implemented on the HIP path; the nearest '
+                                      'available method is "eam_plus" (ihu without its iterations)')
+        if kwargs:
+            raise TypeError(f"upscale: unexpected keyword arguments for method {method}: {sorted(kwargs)}")
+        cellsize, upa, effarea = self._upscale_inputs("upscale", scale_factor, uparea)
+        idxs_ds1, idxs_out = self._h.upscale(method, cellsize, upa, effarea, self._idx_dtype)
+        shape1 = (-(-self.shape[0] // cellsize), -(-self.shape[1] // cellsize))
+        tr = self.transform
+        transform1 = Affine(tr[0] * scale_factor, tr[1], tr[2], tr[3], tr[4] * scale_factor, tr[5])
+        flw1 = FlwdirRaster(idxs_ds=idxs_ds1, shape=shape1, transform=transform1, ftype=self.ftype, latlon=self.latlon)
+        if not flw1.isvalid:
+            raise ValueError("The upscaled flow direction network is invalid. "
+                             + "Please provide a minimal reproducible example.")
+        return flw1, idxs_out.reshape(shape1)
+
+    def upscale_error(self, other, idxs_out):
+        """uint8 array of ``other.shape``: 1 where the first outlet cell downstream of a coarse cell's outlet lies in the
+        cell its upscaled flow direction points to, 0 where not, 255 (-1) where the coarse cell has no data; reference
+        pyflwdir/pyflwdir.py:1093-1121, upscale.py:1312-1363.  ``self`` is the fine raster, ``other`` the upscaled one."""
+        assert self._mv == other._mv
+        if self._d8 is None:
+            raise ValueError("The upscale method only works for D8 or LDD flow directon data.")
+        if self._row_blocks_needed() > 1:
+            raise NotImplementedError("upscale_error: the walks along the fine flow directions have no form beyond "
+                                      "2**32 - 2 cells")
+        if self._has_loop():
+            raise ValueError("upscale_error: the flow direction raster holds a loop; the walks to the next outlet would "
+                             "never end")
+        idxs_out = np.ascontiguousarray(other._check_data(idxs_out, "idxs_out"), dtype=self._idx_dtype)
+        idxs_ds1 = np.ascontiguousarray(other.idxs_ds, dtype=self._idx_dtype)
+        return self._h.upscale_error(idxs_out, idxs_ds1).reshape(other.shape)
+
+    def ucat_outlets(self, cellsize, uparea=None, method="eam_plus"):
+        """Linear indices of the unit catchment outlet cell of every ``cellsize`` x ``cellsize`` block (the missing value
+        where a block holds no candidate); reference pyflwdir/pyflwdir.py:1125-1157, subgrid.py:13-48."""
+        methods = ["eam_plus", "dmm"]
+        method = str(method).lower()
+        if method not in methods:
+            methodstr = "', '".join(methods)
+            raise ValueError(f"Unknown method: {method}, select from: '{methodstr}'")
+        cellsize, upa, effarea = self._upscale_inputs("ucat_outlets", cellsize, uparea)
+        idxs_out = self._h.upscale(method, cellsize, upa, effarea, self._idx_dtype, outlets_only=True)
+        return idxs_out.reshape(-(-self.shape[0] // cellsize), -(-self.shape[1] // cellsize))
+
     def floodplains(self, elevtn, uparea=None, upa_min=1000, b=0.3):
         """Floodplain boundaries from a HAND threshold that scales with upstream area, h ~ A**b (Nardi et al
         2019); reference pyflwdir/pyflwdir.py:1513-1545 + pyflwdir/dem.py:333-379.  int8: 1 floodplain, 0 not,
@@ -1380,6 +1475,21 @@ class FlwdirRaster(object):
 
 
 _NARROW_INT = (np.dtype(np.int8), np.dtype(np.int16), np.dtype(np.uint8), np.dtype(np.uint16))
+
+
+def _effective_area_mask(cellsize, shape, r_ratio=0.5):
+    """uint8 [min(cellsize, nrow), min(cellsize, ncol)]: 1 where the fine cell at (row % cellsize, col % cellsize) lies in
+    the effective area of its coarse cell; reference pyflwdir/upscale.py:214-223, the same float64 expression — Python
+    floats, ``x ** 0.5`` per distinct distance and IEEE additions — evaluated once per cellsize instead of per cell (the
+    device compares bytes and never takes a square root)."""
+    R = cellsize * r_ratio
+    offset = cellsize / 2.0 - 0.5
+    d = [abs(i - offset) for i in range(cellsize)]
+    root = np.array([x ** 0.5 for x in d], np.float64)
+    near = np.array([x <= 0.5 for x in d], bool)
+    mrow, mcol = min(cellsize, shape[0]), min(cellsize, shape[1])
+    ea = ((root[:mrow, None] + root[None, :mcol]) <= R ** 0.5) | near[:mrow, None] | near[None, :mcol]
+    return np.ascontiguousarray(ea).view(np.uint8)
 
 
 def _payload_args(flat, nodata):
