@@ -22,6 +22,14 @@
 //    the tile's pointers that points at itself: no compare / select per cell and round;
 //  * one (local) / two (final) barriers per round: the "is any pointer still moving" vote goes through two
 //    alternating LDS flag rows written by the wave leaders instead of three barriers of __syncthreads_or.
+// The memory phases are the other half, and there the unit is the round trip, not the instruction: the final pass asks
+// for everything its prologue needs — 4 code words, the slot's record, the 5 candidate totals — in ONE batch, nothing
+// waiting in front of the candidates (their addresses come out of registers, fy_cand_row / fy_cand_col), keeps a 16-bit
+// nodata mask instead of the code words for the output (no scratch) and writes one 16-byte store per quad.  Where the
+// waits end up is the compiler's decision and small things in the source move them (a select sunk into a branch, a
+// table in constant memory): the claim above is checked in the disassembly (hipcc ... --cuda-device-only -S: ten
+// global_load_dword, then the first s_waitcnt vmcnt; no scratch_ instruction; four global_store_dwordx4) and in
+// -Rpass-analysis=kernel-resource-usage (ScratchSize 0, <= 80 VGPRs, occupancy 6) after every change to a load.
 #pragma once
 #include <type_traits>
 
@@ -67,10 +75,12 @@ __device__ __forceinline__ bool fx_vote(u32 (*s_flag)[4], int round, u32 tid, bo
 
 // Where the neighbours of perimeter cell p that lie OUTSIDE the tile live: per slot p up to 5 candidates (3 along an
 // edge, 5 at a corner), each 12 bits pslot | tile delta << 8 (xr_t12) plus the direction k << 12; unused entries name
-// the cell's own slot with k = 8 (a bit no source mask has).  A per-lane constant of the final pass (16 bytes): an
-// entry pulls the totals of the exits that drain into it, and because the candidates are known up front all five
-// loads go out with the first instructions of the kernel — speculatively, the record's source mask (loaded beside them)
-// picks the ones that count.
+// the cell's own slot with k = 8 (a bit no source mask has).  An entry of the final pass pulls the totals of the exits
+// that drain into it, and because the candidates follow from the slot alone all five loads go out with the kernel's
+// first loads — speculatively, the record's source mask (loaded beside them) picks the ones that count.
+// make_nbr_tab() states the rule cell by cell; fy_cand_row() / fy_cand_col() are what the kernel runs: the same entries from a handful of
+// selects (no table in memory: a per-lane table load was a round trip of its own in front of the five loads).  The
+// static_assert below holds the two together.
 struct NbrTab {
   uint16_t v[PSL][8];
 };
@@ -97,7 +107,67 @@ constexpr NbrTab make_nbr_tab() {
   }
   return t;
 }
-static __device__ __constant__ const NbrTab NBR_TAB = make_nbr_tab();
+// The five candidates of slot p.  0..2: the cells across the slot's edge, at t - 1, t, t + 1 along it (t: the cell's
+// column for a row slot, its row for a column slot); 3, 4: a corner's two more neighbours, in the tile beside it.  All
+// but the ends of an edge are "a constant of the side + t"; a wave of the kernel holds 64 consecutive slots, so which
+// form applies (and, for the rows, which side) is uniform over the wave and the constants sit in scalar registers.
+#define FY_E(ps, d, k) ((u32)(ps) | (u32)(d) << 8 | (u32)(k) << 12)
+#define FY_UNUSED FY_E(0, 4, 8)
+__host__ __device__ constexpr void fy_cand_row(u32 p, bool hi, u32 *e) {  // p < 2 TS; hi: bottom row (p >= TS)
+  const u32 t = p & (TS - 1u);
+  const bool first = t == 0u, last = t == TS - 1u;
+  // across the edge: the bottom row of the tile above (slots TS + c, tile delta 1) / the top row of the tile below
+  // (slots c, delta 7); k = NW, N, NE / SW, S, SE
+  const u32 k0 = hi ? FY_E(0, 7, 3) : FY_E(TS, 1, 5), k1 = hi ? FY_E(0, 7, 2) : FY_E(TS, 1, 6), k2 = hi ? FY_E(0, 7, 1) : FY_E(TS, 1, 7);
+  const u32 w0 = hi ? FY_E(TS - 1, 6, 3) : FY_E(2 * TS - 1, 0, 5);  // t - 1 = -1: last column of the tile left of that one
+  const u32 w2 = hi ? FY_E(0, 8, 1) : FY_E(TS, 2, 7);               // t + 1 = TS: first column of the tile right of it
+  const u32 a0 = k0 + t - 1u, a2 = k2 + t + 1u;
+  e[0] = first ? w0 : a0;
+  e[1] = k1 + t;
+  e[2] = last ? w2 : a2;
+  // a corner: the cell beside it in its row (W / E) and the one diagonally inward of that, both in the tile beside
+  const u32 l3 = hi ? FY_E(2 * TS - 1, 3, 4) : FY_E(TS - 1, 3, 4), r3 = hi ? FY_E(TS, 5, 0) : FY_E(0, 5, 0);
+  const u32 l4 = hi ? FY_E(4 * TS - 5, 3, 5) : FY_E(3 * TS - 2, 3, 3), r4 = hi ? FY_E(3 * TS - 3, 5, 7) : FY_E(2 * TS, 5, 1);
+  const u32 un = p | FY_UNUSED;
+  const u32 c3 = last ? r3 : un, c4 = last ? r4 : un;
+  e[3] = first ? l3 : c3;
+  e[4] = first ? l4 : c4;
+}
+__host__ __device__ constexpr void fy_cand_col(u32 p, u32 *e) {  // 2 TS <= p < PSL
+  const bool hi = p >= 3u * TS - 2u;  // right column
+  const u32 t = p - (hi ? 3u * TS - 3u : 2u * TS - 1u);  // the cell's row, 1 .. TS - 2
+  // across the edge: the right column of the tile to the left (slots 3 TS - 3 + r, delta 3; k = NW, W, SW) / the left
+  // column of the tile to the right (slots 2 TS - 1 + r, delta 5; k = NE, E, SE); rows 0 and TS - 1 of those columns
+  // are slots of the tile's top / bottom row
+  const u32 k0 = hi ? FY_E(2 * TS - 1, 5, 7) : FY_E(3 * TS - 3, 3, 5), k1 = hi ? FY_E(2 * TS - 1, 5, 0) : FY_E(3 * TS - 3, 3, 4);
+  const u32 k2 = hi ? FY_E(2 * TS - 1, 5, 1) : FY_E(3 * TS - 3, 3, 3);
+  const u32 w0 = hi ? FY_E(0, 5, 7) : FY_E(TS - 1, 3, 5), w2 = hi ? FY_E(TS, 5, 1) : FY_E(2 * TS - 1, 3, 3);
+  const u32 a0 = k0 + t - 1u, a1 = k1 + t, a2 = k2 + t + 1u;
+  const u32 b0 = t == 1u ? w0 : a0, b2 = t == TS - 2u ? w2 : a2;
+  const bool used = p < (u32)NPERIM;
+  e[0] = used ? b0 : FY_UNUSED;
+  e[1] = used ? a1 : FY_UNUSED;
+  e[2] = used ? b2 : FY_UNUSED;
+  e[3] = e[4] = used ? (p | FY_UNUSED) : FY_UNUSED;
+}
+constexpr bool fy_cand_matches_tab() {  // the same set of entries per slot (their order does not matter: they are summed)
+  const NbrTab t = make_nbr_tab();
+  for (u32 p = 0; p < PSL; ++p) {
+    u32 e[5] = {};
+    if (p < 2u * TS) fy_cand_row(p, p >= (u32)TS, e);
+    else fy_cand_col(p, e);
+    for (int i = 0; i < 5; ++i) {
+      int in_tab = 0, in_cand = 0;
+      for (int j = 0; j < 8; ++j) in_tab += t.v[p][j] == e[i] ? 1 : 0;
+      for (int j = 0; j < 5; ++j) in_cand += e[j] == t.v[p][i] ? 1 : 0;
+      if (!in_tab || !in_cand) return false;
+    }
+    for (int j = 5; j < 8; ++j)
+      if ((t.v[p][j] >> 12) != 8) return false;
+  }
+  return true;
+}
+static_assert(fy_cand_matches_tab(), "fy_cand_row() / fy_cand_col() and make_nbr_tab() disagree");
 
 // Weight of the cell in column c of a row with quantised area base + f / 2^32: base + floor((c + 1) f) - floor(c f)
 // (Bresenham along the row).  Rounding every cell of a row the same way would give a run of k cells the error
@@ -370,7 +440,7 @@ __global__ void __launch_bounds__(256) k_tile_local_fast(TileArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 // final pass of an interior tile: the doubling with values; entries start with 1 + inflow
 // ---------------------------------------------------------------------------------------------------------------
-template <bool WEIGHTS, int NT>
+template <bool WEIGHTS, int NT, bool ALIGNED>
 __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileArgs a) {
   constexpr int QF = TCELLS / 4 / NT;   // quads per thread (4 with 256 threads, 2 with 512)
   constexpr u32 QSTR = 4u * NT;         // cells between a thread's quads
@@ -386,21 +456,25 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
   const u32 sbase = sslot_base(tr, tc, a.nstc);
   const i64 r0 = (i64)tr * TS, c0 = (i64)tc * TS;
   const u32 lcq = 4u * (tid & 15u);
+  // ---- the loads of the prologue: ONE batch ----------------------------------------------------------------------
+  // Flow entering at this perimeter cell is pulled from the exits that drain into it.  Where those exits live follows
+  // from the slot alone (fy_cand_row / fy_cand_col: registers, no table in memory), so the candidates' totals are asked for together with
+  // the codes and the record — nothing waits in front of them; the record's source mask selects after the decode.
+  const u32 ptid = tid & 255u;  // (NT = 512: threads 256.. repeat the loads of 0..255 and drop them)
   u32 cq[QF];
 #pragma unroll
   for (int j = 0; j < QF; ++j)
     __builtin_memcpy(&cq[j], a.ncode + (size_t)(r0 + (tid >> 4) + RSTR * j) * a.ncol + (size_t)(c0 + lcq), 4);
-  // flow entering at this perimeter cell: pulled from the exits that drain into it.  All candidates are loaded right
-  // away (NBR_TAB: no load waits for another), the record's source mask selects after the decode below.
-  const u32 ptid = tid & 255u;  // (NT = 512: threads 256.. repeat the loads of 0..255 and drop them)
-  const u32 rec = tid < 256u ? a.xrec[sbase + ptid] : 0u;  // (256 slots per tile; slots 252..255 carry no source mask)
+  u32 rec = a.xrec[sbase + ptid];  // (256 slots per tile; slots 252..255 carry no source mask)
   u32 xc[5], xk[5];
   {
-    const uint4 nb = *reinterpret_cast<const uint4 *>(NBR_TAB.v[ptid]);
     // slot base of the neighbouring tile with delta code (lane & 15), fetched per candidate with a lane permute
     const u32 dl = min(tid & 15u, 8u), ql = (dl * 11u) >> 5;
     const u32 nbase = sslot_base(tr + ql - 1u, tc + (dl - 3u * ql) - 1u, a.nstc);
-    const u32 e5[5] = {nb.x & 0xFFFFu, nb.x >> 16, nb.y & 0xFFFFu, nb.y >> 16, nb.z & 0xFFFFu};
+    const u32 p0 = (u32)__builtin_amdgcn_readfirstlane((int)ptid);  // (first slot of the wave, a multiple of 64)
+    u32 e5[5];
+    if (p0 < 2u * TS) fy_cand_row(ptid, p0 >= (u32)TS, e5);
+    else fy_cand_col(ptid, e5);
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       const u32 bs = (u32)__shfl((int)nbase, (int)(((tid & 48u) | ((e5[i] >> 8) & 15u))));
@@ -408,6 +482,7 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
       xk[i] = e5[i] >> 12;
     }
   }
+  if (NT != 256) rec = tid < 256u ? rec : 0u;  // (a select after the load: no exec-masked region with a wait in it)
   const u32 sink = FY_SINK0 + 4u * (tid & 63u);
   if (tid < 64u) P[TCELLS + tid] = (uint16_t)sink;  // a sink's pointer word points at the sink
 
@@ -421,6 +496,7 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
   }
   u32 pc[QF * 4], qn[QF * 4];
   bool lv[QF];
+  u32 vm = 0;  // bit 4 j + s: register slot s of quad j holds a cell (not nodata) — all the output needs of the codes
 #pragma unroll
   for (int j = 0; j < QF; ++j) {
     const u32 lr = (tid >> 4) + RSTR * j;
@@ -435,9 +511,10 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
       const bool go = __popc(c & ~(rm | cm[s])) == 1u;
       const u32 lt = (u32)((int)(l0 + (sh[s] >> 3)) + fx_sext8(__builtin_amdgcn_perm(FX_TP_HI, FX_TP_LO, fx_ffbl(c))));
       pc[4 * j + s] = go ? (PHYS(lt) << 2) : sink;
-      u32 wv = 1u;
-      if (WEIGHTS) wv = (u32)a.weights[(size_t)(r0 + lr) * a.ncol + (size_t)(c0 + lcq + (sh[s] >> 3))];
-      w4[s] = c != D8_MV ? wv : 0u;
+      const u32 ok = c != D8_MV ? 1u : 0u;
+      vm |= ok << (4 * j + s);
+      w4[s] = ok;
+      if (WEIGHTS) w4[s] = ok ? (u32)a.weights[(size_t)(r0 + lr) * a.ncol + (size_t)(c0 + lcq + (sh[s] >> 3))] : 0u;
     }
     *(uint4 *)&A[l0] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
     *(uint2 *)&P[l0] = make_uint2(pc[4 * j + 0] | (pc[4 * j + 1] << 16), pc[4 * j + 2] | (pc[4 * j + 3] << 16));
@@ -520,21 +597,19 @@ __global__ void __launch_bounds__(NT, NT == 256 ? 6 : 8) k_tile_final_fast(TileA
   }
   if (live) atomicAdd((unsigned long long *)&a.ctrl[T_UNSAT], (unsigned long long)live);
 
-  // ---- write the finished tile (16 B per lane) -----------------------------------------------------------------
+  // ---- write the finished tile: one 16-byte store per quad (ALIGNED, chosen by the host) or four dwords ------------
 #pragma unroll
   for (int j = 0; j < QF; ++j) {
     const u32 l0 = 4u * tid + QSTR * j;
-    const u32 c4 = cq[j];
     const uint4 a4 = *(const uint4 *)&A[l0];
-    const u32 x0 = (qs & 1u) ? a4.y : a4.x, x1 = (qs & 1u) ? a4.x : a4.y;  // undo the swizzle: logical cell k sits in slot k ^ qs
-    const u32 x2 = (qs & 1u) ? a4.w : a4.z, x3 = (qs & 1u) ? a4.z : a4.w;
-    i32 o4[4] = {(i32)((qs & 2u) ? x2 : x0), (i32)((qs & 2u) ? x3 : x1), (i32)((qs & 2u) ? x0 : x2),
-                 (i32)((qs & 2u) ? x1 : x3)};
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-      if (((c4 >> (8 * b)) & 0xFFu) == D8_MV) o4[b] = -9999;
+    const u32 y0 = (vm >> (4 * j + 0)) & 1u ? a4.x : (u32)-9999, y1 = (vm >> (4 * j + 1)) & 1u ? a4.y : (u32)-9999;
+    const u32 y2 = (vm >> (4 * j + 2)) & 1u ? a4.z : (u32)-9999, y3 = (vm >> (4 * j + 3)) & 1u ? a4.w : (u32)-9999;
+    const u32 x0 = (qs & 1u) ? y1 : y0, x1 = (qs & 1u) ? y0 : y1;  // undo the swizzle: logical cell k sits in slot k ^ qs
+    const u32 x2 = (qs & 1u) ? y3 : y2, x3 = (qs & 1u) ? y2 : y3;
+    const i32 o4[4] = {(i32)((qs & 2u) ? x2 : x0), (i32)((qs & 2u) ? x3 : x1), (i32)((qs & 2u) ? x0 : x2),
+                       (i32)((qs & 2u) ? x1 : x3)};
     i32 *dst = a.out + (size_t)(r0 + (tid >> 4) + RSTR * j - a.row_first) * a.ncol + (size_t)(c0 + lcq);
-    if ((((size_t)dst) & 15) == 0) {
+    if (ALIGNED) {
       *(int4 *)dst = make_int4(o4[0], o4[1], o4[2], o4[3]);
     } else {
 #pragma unroll

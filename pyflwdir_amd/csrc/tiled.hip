@@ -613,9 +613,15 @@ __device__ __forceinline__ bool wg_vote(u32 (*s_flag)[NWAVES], int round, u32 ti
 
 // The exit lists.  The supertile solve wants its exits — a third of the slots on real rasters — as a dense list: only
 // exits get an LDS word (72 KB instead of 96 KB: two workgroups per CU), the rounds run without idle lanes, and the
-// solve's own memory accesses become one coalesced, unpredicated, INDEPENDENT batch (round 3 measured the
+// solve's own memory accesses become coalesced, unpredicated, INDEPENDENT batches (round 3 measured the
 // positional kernel: of 79 us per supertile 17 went into streaming 64 KB of xtgt to find the exits, 25 into the
-// dependent loads xtgt -> elink[xtgt] of a third of the lanes, 19 into its scattered outputs).  The lists are built
+// dependent loads xtgt -> elink[xtgt] of a third of the lanes, 19 into its scattered outputs).  "Independent" is a
+// property of the compiled code, not of the source: super_solve loads a batch of (slot, next) pairs for all of a thread's
+// entries, then their start values, then stores to LDS — written with `continue` per entry the same loop compiled to a
+// load, a wait, the dependent load and a wait PER ENTRY (28 serial round trips per workgroup), and the final solve's
+// boundary pulls and its last stores (which reloaded the slots) added 17 more.  Verified in the disassembly of
+// k_super<false> / <true>: the ushort loads of a batch, partial waits (vmcnt(n), n > 0) as the dword loads that depend
+// on them go out, no vmcnt(0) before the barrier; no scratch, occupancy 6.  The lists are built
 // once per pass by one workgroup per TILE (fully parallel, high occupancy): the list index of an exit is the number
 // of exits before it in the supertile — the local tile pass left one ballot word per 64 slots (xmask), a prefix over
 // the supertile's 256 words gives the index; the exit's next hop (elink[xtgt]) is resolved here as well, as the list
@@ -722,7 +728,26 @@ __global__ void __launch_bounds__(256) k_boundary_records(SuperArgs s) {
 #ifndef SNT
 #define SNT 512u
 #endif
-template <bool FINAL, u32 CAP, u32 NT>
+// nbr_slot() for cell (R, C) on the boundary of supertile (str, stc) — the slot of its neighbour in direction k, a cell
+// outside the supertile —, as straight-line code: the final solve works out the slots of all its pulls first and then
+// asks for them in one batch (a branch between two loads is where the compiler puts a wait).
+__device__ __forceinline__ u32 sb_nbr_slot(u32 str, u32 stc, u32 R, u32 C, u32 k, u32 nstc) {
+  const int nr = (int)R + fx_sext8(__builtin_amdgcn_perm(0xFFFFFF00u, 0x01010100u, k));  // d8_dr(k), d8_dc(k)
+  const int nc = (int)C + fx_sext8(__builtin_amdgcn_perm(0x0100FFFFu, 0xFF000101u, k));
+  const u32 lr = (u32)nr & (TS - 1u), lc = (u32)nc & (TS - 1u);
+  // pslot(lr, lc) of a perimeter cell
+  const u32 p_top = lc, p_bot = TS + lc, p_left = 2u * TS - 1u + lr, p_right = 3u * TS - 3u + lr;
+  const u32 p_col = lc == 0u ? p_left : p_right;
+  const u32 p_low = lr == TS - 1u ? p_bot : p_col;
+  const u32 ps = lr == 0u ? p_top : p_low;
+  return sslot_base(str * SG + (u32)(nr >> 6), stc * SG + (u32)(nc >> 6), nstc) + ps;  // (arithmetic shifts: -1 -> -1)
+}
+
+// SKIP: the workgroup leaves when the supertile holds more exits than the capacity in force (k_super; k_exit_lists
+// flagged it by the same test and k_super_flagged takes it) — decided from the count, a scalar load, not from a flag
+// byte that would be waited for alone.  The list loads depend on neither: every list holds SSL entries per supertile
+// (TiledRun::init), so a load at an index past the count stays inside the supertile's own entries and is dropped.
+template <bool FINAL, u32 CAP, u32 NT, bool SKIP = false>
 __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
   constexpr int NW = NT / 64;
   __shared__ u32 T[CAP];
@@ -739,43 +764,90 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
     const u32 row = st / s.nstc;
     if (row != 0 && row != (s.ntr - 1) / SG && row != (s.ntr >= 2 ? (s.ntr - 2) / SG : 0u)) return;
   }
-  const u32 n = s.scount[st];
   constexpr int NSB = SBN / NT;
+  constexpr int BT = DPT < 8 ? DPT : 8;  // list entries per thread and batch (registers: 3 words per entry in flight)
+  static_assert(DPT % BT == 0 && DPT % 2 == 0 && CAP <= SSL, "list batches");
+  const u32 n = s.scount[st];
+  // (the supertile's own stretch of every array: a uniform base and a small per-lane offset, no 64-bit lane addresses)
+  const uint16_t *__restrict__ const ls = s.xl_slot + base, *__restrict__ const ln = s.xl_next + base;
+  const u32 *__restrict__ const xTb = s.xT + base;
   u32 sbr[NSB];  // FINAL: the boundary records of the supertile (asked for first: their totals are a dependent load)
 #pragma unroll
   for (int hh = 0; hh < NSB; ++hh) sbr[hh] = FINAL ? s.sb[(size_t)st * SBN + NT * hh + tid] : 0u;
-  // ---- the exits: list entry -> slot, start value, next hop; dense loads but for the start value ----
-  u32 sxbits = 0;  // bit k: own exit k (tid + 1024 k) drains into another supertile
-#pragma unroll 4
-  for (int k = 0; k < DPT; ++k) {
-    const u32 e = tid + NT * k;
-    if (e >= n) continue;
-    const u32 w = s.xl_slot[base + e];
-    u32 nx = s.xl_next[base + e];
-    const u32 t = s.xT[base + (w & (SSL - 1))];
-    if (w & XL_SX) {  // a super-exit is a root; its list entry names its target instead of a next hop
-      if (!FINAL) sxbits |= 1u << k;
-      nx = e | SDONE;
+  // ---- the exits: list entry -> slot, start value, next hop.  Per batch: every (slot, next) pair of the thread, then
+  //      every start value (the one dependent load), then the LDS stores — two waits per batch, whatever the count ----
+  u32 sxbits = 0;        // bit k: own exit k (tid + NT k) drains into another supertile
+  u32 slot2[DPT / 2];    // FINAL: the exits' slots, two per register, for the totals written at the end
+  u32 w[BT], nx[BT];
+#pragma unroll
+  for (int i = 0; i < BT; ++i) {
+    w[i] = ls[tid + NT * i];
+    nx[i] = ln[tid + NT * i];
+  }
+  if (SKIP && n > s.scap) return;
+#pragma unroll
+  for (int k0 = 0; k0 < DPT; k0 += BT) {
+    u32 t[BT];
+    if (k0) {
+#pragma unroll
+      for (int i = 0; i < BT; ++i) {
+        w[i] = ls[tid + NT * (k0 + i)];
+        nx[i] = ln[tid + NT * (k0 + i)];
+      }
     }
-    T[e] = t;
-    P[e] = (uint16_t)nx;
+#pragma unroll
+    for (int i = 0; i < BT; ++i) t[i] = xTb[w[i] & (SSL - 1)];
+#pragma unroll
+    for (int i = 0; i < BT; ++i) {
+      const int k = k0 + i;
+      const u32 e = tid + NT * k;
+      const bool sx = e < n && (w[i] & XL_SX);  // a super-exit is a root; its list entry names its target instead of a next hop
+      if (!FINAL) sxbits |= sx ? 1u << k : 0u;
+      if (FINAL) slot2[k / 2] = (k & 1) ? (slot2[k / 2] | (w[i] & (SSL - 1)) << 16) : (w[i] & (SSL - 1));
+      T[e] = t[i];  // (entries past the count: never read — the rounds below start from e < n)
+      P[e] = (uint16_t)(sx ? (e | SDONE) : nx[i]);
+    }
   }
   __syncthreads();
   if (FINAL) {
     // flow entering the supertile: the totals of the super-exits that drain into its boundary cells (left on their
-    // slots by the level-3 solve), added to the exit the cell's in-tile path reaches
+    // slots by the level-3 solve), added to the exit the cell's in-tile path reaches.  A boundary cell has 3 outward
+    // neighbours (5 at a corner): the first three bits of every record's mask are pulled in one batch — a slot of the
+    // supertile's own where a bit is missing, its value dropped —, a corner's last two in the loop behind it.
     const u32 str = st / s.nstc, stc = st % s.nstc;
+    u32 pv[NSB][3], mrest[NSB];
+#pragma unroll
+    for (int h = 0; h < NSB; ++h) {
+      u32 R, C;
+      sb_cell(tid + NT * h, &R, &C);
+      u32 m = (sbr[h] & SB_VALID) ? (sbr[h] >> 16) & 0xFFu : 0u;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const u32 sl = sb_nbr_slot(str, stc, R, C, (u32)(__ffs((int)m) - 1) & 7u, s.nstc);
+        pv[h][i] = m ? sl : base;
+        m &= m - 1u;
+      }
+      mrest[h] = m;
+    }
+#pragma unroll
+    for (int h = 0; h < NSB; ++h) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) pv[h][i] = s.xtot[pv[h][i]];
+    }
 #pragma unroll
     for (int h = 0; h < NSB; ++h) {
       const u32 r = sbr[h];
       if (!(r & SB_VALID)) continue;
-      u32 R, C;
-      sb_cell(tid + NT * h, &R, &C);
-      u32 m = (r >> 16) & 0xFFu, v = 0;
-      while (m) {
-        const int k = __ffs((int)m) - 1;
-        m &= m - 1u;
-        v += s.xtot[nbr_slot(str * SG + (R >> 6), stc * SG + (C >> 6), (int)(R & 63u), (int)(C & 63u), k, s.nstc)];
+      const u32 m0 = (r >> 16) & 0xFFu, m1 = m0 & (m0 - 1u), m2 = m1 & (m1 - 1u);
+      u32 m = mrest[h], v = pv[h][0] + (m1 ? pv[h][1] : 0u) + (m2 ? pv[h][2] : 0u);  // (m0 != 0: the record is valid)
+      if (m) {
+        u32 R, C;
+        sb_cell(tid + NT * h, &R, &C);
+        while (m) {
+          const int k = __ffs((int)m) - 1;
+          m &= m - 1u;
+          v += s.xtot[nbr_slot(str * SG + (R >> 6), stc * SG + (C >> 6), (int)(R & 63u), (int)(C & 63u), k, s.nstc)];
+        }
       }
       atomicAdd(&T[r & (SSL - 1)], v);
     }
@@ -844,10 +916,10 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
     if (live) atomicAdd((unsigned long long *)&s.ctrl[T_SLIVE], 1ull);  // a cycle inside the supertile
   }
   if (FINAL) {  // the total of every exit, where the tile entries it drains into will pull it
-#pragma unroll 4
+#pragma unroll
     for (int k = 0; k < DPT; ++k) {
       const u32 e = tid + NT * k;
-      if (e < n) s.xtot[base + (s.xl_slot[base + e] & (SSL - 1))] = T[e];
+      if (e < n) (s.xtot + base)[(slot2[k / 2] >> (16 * (k & 1))) & 0xFFFFu] = T[e];  // (the slot: kept from the list phase)
     }
     return;
   }
@@ -904,8 +976,7 @@ __device__ __forceinline__ void super_solve(const SuperArgs &s, const u32 st) {
 
 template <bool FINAL>
 __global__ void __launch_bounds__(SNT, SNT == 512u ? 6 : 8) k_super(SuperArgs s) {
-  if (s.sover[blockIdx.x]) return;  // (more exits than SCAP: k_super_flagged takes it)
-  super_solve<FINAL, SCAP, SNT>(s, blockIdx.x);
+  super_solve<FINAL, SCAP, SNT, true>(s, blockIdx.x);  // (leaves when the supertile is flagged)
 }
 // the supertiles k_exit_lists flagged (contrived rasters only: normally none, and a grid of this 96 KB kernel over all
 // supertiles costs 60-90 us just to find that out): a small fixed grid walks their list
@@ -1752,8 +1823,16 @@ int TiledRun::phase_b_issue() {
   const bool have_i = gridi.x && gridi.y;
   pfd_seg_begin(h, "tile_final");
   if (have_i) {  // (segments: the interior kernel alone, then the frame around it)
-    if (a.weights) k_tile_final_fast<true, FY_NT><<<gridi, FY_NT, 0, h->stream>>>(a);
-    else k_tile_final_fast<false, FY_NT><<<gridi, FY_NT, 0, h->stream>>>(a);
+    // (a quad starts at a column that is a multiple of 4: with rows of 4 n cells and a 16-byte aligned raster every quad
+    //  of the launch is one aligned 16-byte store)
+    const bool al16 = (h->ncol & 3) == 0 && ((uintptr_t)a.out & 15u) == 0;
+    if (a.weights) {
+      if (al16) k_tile_final_fast<true, FY_NT, true><<<gridi, FY_NT, 0, h->stream>>>(a);
+      else k_tile_final_fast<true, FY_NT, false><<<gridi, FY_NT, 0, h->stream>>>(a);
+    } else {
+      if (al16) k_tile_final_fast<false, FY_NT, true><<<gridi, FY_NT, 0, h->stream>>>(a);
+      else k_tile_final_fast<false, FY_NT, false><<<gridi, FY_NT, 0, h->stream>>>(a);
+    }
     pfd_seg_end(h, 1);
     pfd_seg_begin(h, "tile_final_frame");
   }
