@@ -5,6 +5,8 @@ must be identical to the single-handle result and to the oracle for every block 
 import numpy as np
 import pytest
 
+import local_equations as LE
+
 pytestmark = pytest.mark.gpu
 
 
@@ -283,7 +285,12 @@ def test_up_block_verifier_sees_a_wrong_cell(gpu_lib, oracle):
         assert h.accuflux_block(payload, code, seed, out, -9999, -9999.0, 1, verify=True)[1] == 0
         r, c = np.argwhere((d8[a + 1:e] != 247) & (d8[a + 1:e] != 0))[1234]
         out[r + 1, c] += np.float32(1.0)
-        assert h.accuflux_block(payload, code, seed, out, -9999, -9999.0, 1, verify=True)[1] == 2
+        # the count of the independent restatement (tests/local_equations.py) on the whole raster with the block's rows
+        # in place, own rows only
+        whole = exp.copy()
+        whole[a:e] = out
+        n_bad = int(LE.accuflux_up(LE.Graph(idxs_ds, d8.shape), data, whole, nodata=-9999)[0].reshape(d8.shape)[a + 1:e].sum())
+        assert h.accuflux_block(payload, code, seed, out, -9999, -9999.0, 1, verify=True)[1] == n_bad == 2
     finally:
         h.close()
 

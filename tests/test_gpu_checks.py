@@ -4,6 +4,8 @@ any perturbed one; the statistics must equal numpy's on the oracle's arrays."""
 import numpy as np
 import pytest
 
+import local_equations as LE
+
 pytestmark = pytest.mark.gpu
 
 
@@ -34,11 +36,15 @@ def test_stats_and_verifier(gpu_lib, oracle, shape, kw):
     i = int(seq[len(seq) // 2])
     bad[i] += 1
     vb = h.verify_upstream_area_cell(bad)
-    assert vb["bad_cells"] >= 1
+    # exactly what the independent restatement of the local equations counts (tests/local_equations.py): the cell and
+    # the cell it drains into, every other figure as numpy gives it
+    g = LE.Graph(idxs_ds, shape)
+    assert vb == LE.upa_cell_stats(g, bad) and vb["bad_cells"] == (1 if idxs_ds[i] == i else 2)
     if n_valid < d8.size:
         bad = upa.copy()
         bad[np.flatnonzero(d8.ravel() == 247)[0]] = 0
-        assert h.verify_upstream_area_cell(bad)["bad_nodata"] == 1
+        vb = h.verify_upstream_area_cell(bad)
+        assert vb["bad_nodata"] == 1 and vb == LE.upa_cell_stats(g, bad)
     h.close()
 
 
