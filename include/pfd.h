@@ -64,6 +64,7 @@ extern "C" {
 /* accumulation direction: streams.accuflux (up) / streams.accuflux_ds (down) */
 #define PFD_UP 0
 #define PFD_DOWN 1
+#define PFD_BOTH 2 /* pfd_segment_slope only: fixed_length_slope around the outlet */
 
 /* fillnodata: how the upstream values meet at a confluence (direction "down") */
 #define PFD_FILL_MAX 0
@@ -446,6 +447,49 @@ int pfd_fill_depressions(int dtype, const void *elevtn, int64_t nrow, int64_t nc
  * engine's 32-bit order) — as does pfd_basins, which otherwise runs at any size too. */
 int pfd_ucat_area(pfd_raster *h, const int64_t *idxs_out, int64_t k, int map_dtype, void *map_out, int memspace,
                   int area_dtype, const void *area_rows, void *area_out);
+/* subgrid.ucat_volume (reference pyflwdir/subgrid.py:96-142; FlwdirRaster.ucat_volume pyflwdir.py:1193-1225): unit
+ * catchment map and floodplain volume per depth.  `idxs_out`, `map_dtype`, `map_out` and `area_rows` as for pfd_ucat_area
+ * (area_dtype PFD_F32 / PFD_F64); `hand`: n values of hand_dtype (PFD_F32 / PFD_F64); `depths`: ndepths HOST values of
+ * depth_dtype (PFD_F32 / PFD_F64); vol_out: ndepths x k values of depth_dtype, depth-major (-9999 for missing outlets).
+ * `memspace` covers hand, map_out and vol_out.  The arithmetic is the reference's, type by type: dh = max(0, depth - hand)
+ * in the common type of depths and hand, area * dh in the common type of all three, the running column rounded to
+ * depth_dtype after every add, cells added in idxs_seq order.  32-bit cell indices, D8 handles. */
+int pfd_ucat_volume(pfd_raster *h, const int64_t *idxs_out, int64_t k, int map_dtype, void *map_out, int hand_dtype,
+                    const void *hand, int area_dtype, const void *area_rows, int depth_dtype, const void *depths,
+                    int64_t ndepths, void *vol_out, int memspace);
+/* ---- river segments between unit-catchment outlets (csrc/subgrid.hip) ---------------------------------------------
+ * Common arguments: `idxs_out` k outlet cells (HOST int64; < 0 = missing: the result holds nodata there; repeats allowed);
+ * `direction` PFD_DOWN follows the handle's downstream links, PFD_UP the caller's `idxs_us_main` (n indices of idx_dtype,
+ * the dtype's -1 = none; may be NULL for PFD_DOWN); `mask` uint8 (nullable): a walk stops before a cell where it is 0.
+ * `memspace` covers idxs_us_main, mask, the per-cell payloads and `out` (k values).  An index outside the raster and a
+ * walk that does not end within n steps (a cycle) return PFD_EINVAL.  D8 handles with 32-bit cell indices.
+ * pfd_segment_length — subgrid.segment_length (subgrid.py:145-205; FlwdirRaster.subgrid_rivlen pyflwdir.py:1227-1274):
+ *   the walk steps ONTO the next outlet; out = |distnc[last] - distnc[outlet]| in dist_dtype (PFD_I32 cells with nodata
+ *   -9999, PFD_F32 metres with nodata -9999.0).
+ * pfd_segment_slope — subgrid.segment_slope and fixed_length_slope with lstsq=False (subgrid.py:414-559;
+ *   FlwdirRaster.subgrid_rivslp pyflwdir.py:1276-1342): PFD_UP / PFD_DOWN: |dz / dx| between the outlet and the last cell
+ *   BEFORE the next outlet, in elev_dtype (PFD_F32 / PFD_F64), 0 for a one-cell segment; PFD_BOTH: down while
+ *   distnc > distnc[outlet] - length / 2 (or a pit), then up the main stem while distnc < distnc[outlet] + length / 2,
+ *   float32.  `distnc`: n float32.  No mask: the interpreted reference never honours it (`mask[i] is False`).  The
+ *   least-squares form is not offered: its float32 powf and its cancelling denominator cannot be reproduced.
+ * pfd_segment_average — subgrid.segment_average with arithmetics._average (subgrid.py:208-272, arithmetics.py:17-29;
+ *   FlwdirRaster.subgrid_rivavg pyflwdir.py:1344-1398): the weighted mean of the cells from the outlet to the last cell
+ *   BEFORE the next outlet, skipping `nodata` (NaN: isnan); data PFD_F32 / PFD_F64, `weights` of weight_dtype (NULL: ones of
+ *   that dtype); sums in the reference's accumulator types; nodata where the weights sum to 0.
+ * pfd_segment_median — subgrid.segment_median (subgrid.py:277-337): the median of the same cells without nodata and NaN,
+ *   the mean of the two middle values in the data's dtype for an even count, NaN for a segment without values. */
+int pfd_segment_length(pfd_raster *h, const int64_t *idxs_out, int64_t k, int direction, int idx_dtype,
+                       const void *idxs_us_main, const uint8_t *mask, int dist_dtype, const void *distnc, void *out,
+                       int memspace);
+int pfd_segment_slope(pfd_raster *h, const int64_t *idxs_out, int64_t k, int direction, int idx_dtype,
+                      const void *idxs_us_main, int elev_dtype, const void *elevtn, const float *distnc, double length,
+                      void *out, int memspace);
+int pfd_segment_average(pfd_raster *h, const int64_t *idxs_out, int64_t k, int direction, int idx_dtype,
+                        const void *idxs_us_main, const uint8_t *mask, int dtype, const void *data, int weight_dtype,
+                        const void *weights, double nodata, void *out, int memspace);
+int pfd_segment_median(pfd_raster *h, const int64_t *idxs_out, int64_t k, int direction, int idx_dtype,
+                       const void *idxs_us_main, const uint8_t *mask, int dtype, const void *data, double nodata, void *out,
+                       int memspace);
 /* ---- outlets derived from the network: mark -> list in sequence order -> (number, fill) -----------------------------
  * Three calls of the reference are one primitive (csrc/outlets.hip): mark cells by a rule that looks at the cell and its
  * downstream cell, list the marked cells in the order of core.idxs_seq (only cells IN the sequence count: a cell on or

@@ -18,11 +18,13 @@ PFD_HOST, PFD_DEVICE = 0, 1
 PFD_I32, PFD_U32, PFD_I64, PFD_F32, PFD_F64 = 1, 2, 3, 4, 5
 _PAYLOAD_CODE = {np.dtype(np.int32): PFD_I32, np.dtype(np.int64): PFD_I64, np.dtype(np.float32): PFD_F32,
                  np.dtype(np.float64): PFD_F64}
-PFD_UP, PFD_DOWN = 0, 1
+PFD_UP, PFD_DOWN, PFD_BOTH = 0, 1, 2  # (PFD_BOTH: pfd_segment_slope only)
 # fillnodata payload codes beyond the five above (narrow integers travel widened in int32 lanes) and merge rules
 PFD_U64, PFD_I8, PFD_U8, PFD_I16, PFD_U16 = 6, 7, 8, 9, 10
 PFD_FILL_MAX, PFD_FILL_MIN, PFD_FILL_SUM = 0, 1, 2
 UPSCALE_METHOD = {"dmm": 0, "eam": 1, "eam_plus": 2}  # PFD_UPSCALE_*
+
+_FLOAT_CODE = {np.dtype(np.float32): PFD_F32, np.dtype(np.float64): PFD_F64}
 
 IDX_CODE = {np.dtype(np.int32): PFD_I32, np.dtype(np.uint32): PFD_U32, np.dtype(np.int64): PFD_I64}
 
@@ -51,6 +53,7 @@ SYMBOLS = [
     "pfd_streams",
     "pfd_interbasin_mask", "pfd_inflow_idxs", "pfd_basin_bounds", "pfd_subbasins_pfafstetter",
     "pfd_upscale", "pfd_upscale_outlets", "pfd_upscale_error",
+    "pfd_ucat_volume", "pfd_segment_length", "pfd_segment_slope", "pfd_segment_average", "pfd_segment_median",
 ]
 
 _lib = None
@@ -152,6 +155,16 @@ def lib() -> C.CDLL:
         L.pfd_fill_depressions.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int,
                                            C.c_double, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
         L.pfd_ucat_area.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.pfd_ucat_volume.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+        L.pfd_segment_length.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_int]
+        L.pfd_segment_slope.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_double, C.c_void_p, C.c_int]
+        L.pfd_segment_average.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int]
+        L.pfd_segment_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_double, C.c_void_p, C.c_int]
         L.pfd_floodplains.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.pfd_snap_downstream.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         L.pfd_snap.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
@@ -206,6 +219,15 @@ def ptr(a):
     if isinstance(a, DeviceBuffer):
         return C.c_void_p(a.addr)
     return C.c_void_p(int(a))
+
+
+def _payload_pair(a):
+    """(array or DeviceBuffer, dtype code) of a per-cell payload: a C-contiguous numpy array, or a ``(DeviceBuffer, code)``
+    pair passed through."""
+    if isinstance(a, tuple):
+        return a
+    a = np.ascontiguousarray(a)
+    return a, _PAYLOAD_CODE[a.dtype]
 
 
 # state record of the row-block floodplains (csrc/sweeps.hip FloodV): elevation / height threshold of the stream cell that
@@ -667,6 +689,74 @@ class RasterHandle:
         check(lib().pfd_ucat_area(self._h, ptr(idxs_out), idxs_out.size, IDX_CODE[np.dtype(map_dtype)], ptr(ucmap), PFD_HOST,
                                   code, ptr(area_rows), ptr(are)))
         return ucmap, are
+
+    def ucat_volume(self, idxs_out, map_dtype, hand, area_rows, depths, map_out=None, vol_out=None, memspace=PFD_HOST):
+        """(map[n] of map_dtype, volume[depths.size, k] in the dtype of ``depths``) of pfd_ucat_volume; ``hand`` float32 /
+        float64 per cell, ``area_rows`` nrow float32 / float64 row areas.  PFD_DEVICE: ``hand`` (pass its dtype code as a
+        ``(DeviceBuffer, code)`` pair), ``map_out`` and ``vol_out`` are DeviceBuffers and are returned as given."""
+        idxs_out = np.ascontiguousarray(idxs_out, dtype=np.int64).ravel()
+        area_rows, depths = np.ascontiguousarray(area_rows), np.ascontiguousarray(depths)
+        assert area_rows.size == self.nrow
+        hand, hcode = _payload_pair(hand)
+        if memspace == PFD_HOST:
+            map_out, vol_out = np.empty(self.n, map_dtype), np.empty((depths.size, idxs_out.size), depths.dtype)
+        check(lib().pfd_ucat_volume(self._h, ptr(idxs_out), idxs_out.size, IDX_CODE[np.dtype(map_dtype)], ptr(map_out), hcode,
+                                    ptr(hand), _FLOAT_CODE[area_rows.dtype], ptr(area_rows), _FLOAT_CODE[depths.dtype],
+                                    ptr(depths), depths.size, ptr(vol_out), memspace))
+        return map_out, vol_out
+
+    # -- river segments between unit-catchment outlets (csrc/subgrid.hip).  ``idxs_out``: int64, < 0 = missing.  PFD_HOST:
+    #    per-cell arguments are numpy arrays and the result is a new array; PFD_DEVICE: they are DeviceBuffers — payloads as
+    #    ``(DeviceBuffer, dtype code)`` pairs, ``idxs_us_main`` as ``(DeviceBuffer, numpy dtype)`` — and ``out`` is returned.
+    def _segment_args(self, idxs_out, idxs_us_main):
+        idxs_out = np.ascontiguousarray(idxs_out, dtype=np.int64).ravel()
+        if idxs_us_main is None:
+            return idxs_out, None, PFD_I64
+        if isinstance(idxs_us_main, tuple):
+            return idxs_out, idxs_us_main[0], IDX_CODE[np.dtype(idxs_us_main[1])]
+        idxs_us_main = np.ascontiguousarray(idxs_us_main).ravel()
+        assert idxs_us_main.size == self.n
+        return idxs_out, idxs_us_main, IDX_CODE[idxs_us_main.dtype]
+
+    def segment_length(self, idxs_out, direction, idxs_us_main, mask, distnc, out=None, memspace=PFD_HOST):
+        idxs_out, us, icode = self._segment_args(idxs_out, idxs_us_main)
+        distnc, dcode = _payload_pair(distnc)
+        if memspace == PFD_HOST:
+            out = np.empty(idxs_out.size, distnc.dtype)
+        check(lib().pfd_segment_length(self._h, ptr(idxs_out), idxs_out.size, int(direction), icode, ptr(us), ptr(mask), dcode,
+                                       ptr(distnc), ptr(out), memspace))
+        return out
+
+    def segment_slope(self, idxs_out, direction, idxs_us_main, elevtn, distnc, length=1000, out=None, memspace=PFD_HOST):
+        idxs_out, us, icode = self._segment_args(idxs_out, idxs_us_main)
+        elevtn, ecode = _payload_pair(elevtn)
+        if memspace == PFD_HOST:
+            assert distnc.dtype == np.float32
+            out = np.empty(idxs_out.size, np.float32 if direction == PFD_BOTH else elevtn.dtype)
+        check(lib().pfd_segment_slope(self._h, ptr(idxs_out), idxs_out.size, int(direction), icode, ptr(us), ecode, ptr(elevtn),
+                                      ptr(distnc), float(length), ptr(out), memspace))
+        return out
+
+    def segment_average(self, idxs_out, direction, idxs_us_main, mask, data, weights=None, nodata=-9999.0, out=None,
+                        memspace=PFD_HOST):
+        """``weights`` None: float32 ones (the reference's default)."""
+        idxs_out, us, icode = self._segment_args(idxs_out, idxs_us_main)
+        data, dcode = _payload_pair(data)
+        weights, wcode = (None, PFD_F32) if weights is None else _payload_pair(weights)
+        if memspace == PFD_HOST:
+            out = np.empty(idxs_out.size, data.dtype)
+        check(lib().pfd_segment_average(self._h, ptr(idxs_out), idxs_out.size, int(direction), icode, ptr(us), ptr(mask), dcode,
+                                        ptr(data), wcode, ptr(weights), float(nodata), ptr(out), memspace))
+        return out
+
+    def segment_median(self, idxs_out, direction, idxs_us_main, mask, data, nodata=-9999.0, out=None, memspace=PFD_HOST):
+        idxs_out, us, icode = self._segment_args(idxs_out, idxs_us_main)
+        data, dcode = _payload_pair(data)
+        if memspace == PFD_HOST:
+            out = np.empty(idxs_out.size, data.dtype)
+        check(lib().pfd_segment_median(self._h, ptr(idxs_out), idxs_out.size, int(direction), icode, ptr(us), ptr(mask), dcode,
+                                       ptr(data), float(nodata), ptr(out), memspace))
+        return out
 
     # -- outlets derived from the network (csrc/outlets.hip) ------------------------------------------------------
     def _outlet_cap(self):

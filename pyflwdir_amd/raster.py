@@ -1261,6 +1261,145 @@ class FlwdirRaster(object):
         ucat_are[owner] = acc[1:][owner]
         return ucat_map, ucat_are
 
+    @property
+    def distnc(self):
+        """Distance to the outlet [m]: ``stream_distance(unit="m")``, kept under "distnc" when ``cache=True``; reference
+        pyflwdir/pyflwdir.py:420-429."""
+        if "distnc" in self._cached:
+            return self._cached["distnc"]
+        distnc = self.stream_distance(unit="m")
+        if self.cache:
+            self._cached.update(distnc=distnc)
+        return distnc
+
+    # -- the SUBGRID section (csrc/subgrid.hip: label sums and one-lane-per-outlet segment walks, DESIGN.md) -----------
+    def _subgrid_refusals(self, what, walks=True):
+        """What comes before any kernel of the subgrid calls: a raster of the general engine or beyond 32-bit cell
+        indices has no form here, and on a raster with a cycle the reference's ``while True`` walks never return."""
+        if self._d8 is None:
+            raise NotImplementedError(f"{what}: not available on a general idxs_ds graph (links outside the 8 neighbours)")
+        if self._row_blocks_needed() > 1:
+            raise NotImplementedError(f"{what}: the walks along the flow directions have no form beyond 2**32 - 2 cells")
+        if walks and self._has_loop():
+            raise ValueError(f"{what}: the flow direction raster holds a loop; the walks to the next outlet would never end")
+
+    def _subgrid_outlets(self, idxs_out):
+        """(idxs_out as given or every cell, int64 list with -1 for the missing value)"""
+        if idxs_out is None:
+            idxs_out = np.arange(self.size, dtype=np.intp).reshape(self.shape)
+        idxs_out = np.asarray(idxs_out)
+        flat = idxs_out.ravel()
+        idx64 = np.where(flat == self._mv, -1, flat.astype(np.int64)) if flat.size else flat.astype(np.int64)
+        if idx64.size and (idx64.min() < -1 or idx64.max() >= self.size):
+            raise IndexError("idxs outside domain")
+        return idxs_out, idx64
+
+    def _subgrid_float(self, data, name, what):
+        """Flattened float32 / float64 payload; the dtype decides the arithmetic, so nothing is converted."""
+        data = self._check_data(data, name)
+        if data.dtype not in (np.float32, np.float64):
+            raise NotImplementedError(f"{what}: {name} dtype {data.dtype} is not supported on the HIP path "
+                                      "(float32 or float64; the dtype decides the arithmetic, nothing is converted silently)")
+        return np.ascontiguousarray(data)
+
+    def _subgrid_mask(self, mask):
+        mask = self._check_data(mask, "mask", optional=True)
+        return None if mask is None else np.ascontiguousarray(mask != 0).view(np.uint8)
+
+    def _subgrid_us(self, direction):
+        return np.ascontiguousarray(self.idxs_us_main) if direction != "down" else None
+
+    def ucat_volume(self, idxs_out, hand, depths=np.arange(0.5, 3.0, 0.5, dtype=np.float32)):
+        """Unit catchment map (high resolution) and the flood volume [m3] below each of ``depths`` above the nearest drain
+        (low resolution, ``(depths.size, *idxs_out.shape)`` in the dtype of ``depths``); reference
+        pyflwdir/pyflwdir.py:1193-1225 + pyflwdir/subgrid.py:96-142.  ``hand`` and ``depths`` are float32 or float64; the
+        sums follow the reference's cell order and types (float64 products on lat/lon grids, float32-based ones on
+        projected grids, every running sum rounded to the dtype of ``depths``)."""
+        self._subgrid_refusals("ucat_volume", walks=False)
+        idxs_out, idx64 = self._subgrid_outlets(idxs_out)
+        hand = self._subgrid_float(hand, "hand", "ucat_volume")
+        depths = np.atleast_1d(np.asarray(depths))
+        if depths.ndim != 1 or depths.dtype not in (np.float32, np.float64):
+            raise NotImplementedError(f"ucat_volume: depths must be a 1D float32 or float64 array, not {depths.dtype}")
+        rows = np.ascontiguousarray(gis.area_rows(self.transform, self.shape, self.latlon, unit="m2") / gis.AREA_FACTORS["m2"])
+        ucat_map, ucat_vol = self._h.ucat_volume(idx64, self._idx_dtype, hand, rows, np.ascontiguousarray(depths))
+        return ucat_map.reshape(self.shape), ucat_vol.reshape((depths.size, *idxs_out.shape))
+
+    def subgrid_rivlen(self, idxs_out, mask=None, direction="up", unit="cell"):
+        """Subgrid river length: along the path from each unit catchment outlet up- or downstream (upstream: the main
+        upstream cell) up to and including the next outlet, or to the last cell before a masked-out cell, a pit or a
+        headwater; int32 cells with nodata -9999 (``unit="cell"``) or float32 metres (``unit="m"``); reference
+        pyflwdir/pyflwdir.py:1227-1274 + pyflwdir/subgrid.py:145-205.  ``idxs_out=None``: every cell is an outlet."""
+        direction = str(direction).lower()
+        if direction not in ["up", "down"]:
+            raise ValueError(f'Unknown flow direction: {direction}, select from ["up", "down"].')
+        if unit not in ["m", "cell"]:
+            raise ValueError(f'Unknown unit: {unit}, select from ["m", "cell"]')
+        self._subgrid_refusals("subgrid_rivlen")
+        idxs_out, idx64 = self._subgrid_outlets(idxs_out)
+        distnc = self.distnc if unit == "m" else self.stream_distance(unit=unit)
+        rivlen = self._h.segment_length(idx64, _hip.PFD_DOWN if direction == "down" else _hip.PFD_UP, self._subgrid_us(direction),
+                                        self._subgrid_mask(mask), np.ascontiguousarray(distnc.ravel()))
+        return rivlen.reshape(idxs_out.shape)
+
+    def subgrid_rivslp(self, idxs_out, elevtn, length=1000, direction="both", method="mean", mask=None):
+        """Subgrid river slope [m/m] at the unit catchment outlets: ``direction="both"`` between the cells half of
+        ``length`` [m] down- and upstream of the outlet (float32), ``"up"`` / ``"down"`` between the outlet and the last
+        cell before the next outlet (dtype of ``elevtn``); reference pyflwdir/pyflwdir.py:1276-1342 +
+        pyflwdir/subgrid.py:414-559.  ``method="mean"`` only: the reference's least-squares fit squares float32 distances
+        with libm's ``powf`` and divides by a difference that cancels to rounding noise (it returns ``inf`` itself), so
+        ``"lstsq"`` cannot be reproduced and raises NotImplementedError.  ``mask`` is accepted and has no effect, as in the
+        interpreted reference, whose slope loops test ``mask[i] is False``."""
+        direction = str(direction).lower()
+        if direction not in ["both", "up", "down"]:
+            raise ValueError(f'Unknown flow direction: {direction}, select from ["both", "up", "down"].')
+        if method == "lstsq":
+            raise NotImplementedError('subgrid_rivslp: method "lstsq" is not implemented on the HIP path: the reference squares '
+                                      "float32 distances with libm's powf (x ** 2 != x * x for some x) and its denominator "
+                                      'n * sum(x**2) - sum(x)**2 cancels to rounding noise; use method="mean"')
+        elevtn = self._subgrid_float(elevtn, "elevtn", "subgrid_rivslp")
+        self._subgrid_refusals("subgrid_rivslp")
+        idxs_out, idx64 = self._subgrid_outlets(idxs_out)
+        self._check_data(mask, "mask", optional=True)
+        code = {"both": _hip.PFD_BOTH, "up": _hip.PFD_UP, "down": _hip.PFD_DOWN}[direction]
+        rivslp = self._h.segment_slope(idx64, code, self._subgrid_us(direction), elevtn, np.ascontiguousarray(self.distnc.ravel()),
+                                       length)
+        return rivslp.reshape(idxs_out.shape)
+
+    def subgrid_rivavg(self, idxs_out, data, weights=None, nodata=-9999.0, mask=None, direction="up"):
+        """Weighted average of ``data`` over the subgrid river: the path from each unit catchment outlet up- or downstream
+        to the last cell before the next outlet (or before a masked-out cell, a pit, a headwater), cells equal to
+        ``nodata`` skipped; reference pyflwdir/pyflwdir.py:1344-1398 + pyflwdir/subgrid.py:208-272.  ``data`` and
+        ``weights`` (default: float32 ones) are float32 or float64, and the sums run in the types the reference's loop
+        uses for them."""
+        direction = str(direction).lower()
+        if direction not in ["up", "down"]:
+            raise ValueError('Unknown flow direction: {direction}, select from ["up", "down"].')
+        data = self._subgrid_float(data, "data", "subgrid_rivavg")
+        if weights is not None:
+            weights = self._subgrid_float(weights, "weights", "subgrid_rivavg")
+        self._subgrid_refusals("subgrid_rivavg")
+        idxs_out, idx64 = self._subgrid_outlets(idxs_out)
+        rivavg = self._h.segment_average(idx64, _hip.PFD_DOWN if direction == "down" else _hip.PFD_UP, self._subgrid_us(direction),
+                                         self._subgrid_mask(mask), data, weights, nodata)
+        return rivavg.reshape(idxs_out.shape)
+
+    def subgrid_rivmed(self, idxs_out, data, weights=None, nodata=-9999.0, mask=None, direction="up"):
+        """Median of ``data`` over the subgrid river (the segment of ``subgrid_rivavg``), cells equal to ``nodata`` or NaN
+        left out; NaN for a segment without values.  The reference's method (pyflwdir/pyflwdir.py:1400-1454) raises
+        TypeError: it passes ``weights=`` to ``subgrid.segment_median``, which has no such parameter.  Here the call
+        returns what ``subgrid.segment_median`` (pyflwdir/subgrid.py:277-337) computes; ``weights`` is accepted and
+        ignored, as the reference's signature documents."""
+        direction = str(direction).lower()
+        if direction not in ["up", "down"]:
+            raise ValueError('Unknown flow direction: {direction}, select from ["up", "down"].')
+        data = self._subgrid_float(data, "data", "subgrid_rivmed")
+        self._subgrid_refusals("subgrid_rivmed")
+        idxs_out, idx64 = self._subgrid_outlets(idxs_out)
+        rivmed = self._h.segment_median(idx64, _hip.PFD_DOWN if direction == "down" else _hip.PFD_UP, self._subgrid_us(direction),
+                                        self._subgrid_mask(mask), data, nodata)
+        return rivmed.reshape(idxs_out.shape)
+
     # -- upscaling (csrc/upscale.hip: a per-coarse-cell arg-max and per-coarse-cell walks, DESIGN.md) ------------------
     def _has_loop(self):
         """``not isvalid`` without a rank raster on the host: the handle's cell order (kept on the device once built)
