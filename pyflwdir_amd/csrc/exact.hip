@@ -1262,7 +1262,7 @@ int pfd_ensure_xplan(pfd_raster *h, bool allow_block) {
 // debug export (tests / tools): plan summary; not part of the C-ABI contract
 extern "C" int pfd_debug_xplan(pfd_raster *h, int64_t info[8], uint8_t *lh_host) {
   PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_ensure_xplan(h));
+  PFDCHK(pfd_ensure_xplan(h, h->halo_top || h->halo_bot));  // (a row block: the plan its *_block sweeps run on)
   for (int k = 0; k < 8; ++k) info[k] = 0;
   info[0] = h->xplan_state;
   if (h->xplan_state != 1) return PFD_OK;
@@ -1270,11 +1270,19 @@ extern "C" int pfd_debug_xplan(pfd_raster *h, int64_t info[8], uint8_t *lh_host)
   info[1] = p->ntrunk;
   info[2] = p->nchain;
   info[3] = p->nslot;
+  // what the sweeps choose their kernels by: rounds, the two-stream tail (-1: none), the longest chain's slots (0: no
+  // chain of XLONG slots or more), the chains of the largest round (what xfuse_min_chains is compared with)
   int nb = 0;
-  i64 longest = 0;
-  for (int b = 0; b < 32; ++b) nb += p->b_chain[b + 1] > p->b_chain[b];
+  i64 longest = 0, widest = 0;
+  for (int b = 0; b < 32; ++b) {
+    nb += p->b_chain[b + 1] > p->b_chain[b];
+    longest = std::max<i64>(longest, (i64)p->b_maxlen[b]);
+    widest = std::max<i64>(widest, p->b_chain[b + 1] - p->b_chain[b]);
+  }
   info[4] = nb;
-  (void)longest;
+  info[5] = xplan_tail_split(p);
+  info[6] = longest;
+  info[7] = widest;
   if (lh_host) HIPCHK(hipMemcpy(lh_host, p->lh, (size_t)h->n, hipMemcpyDeviceToHost));
   return PFD_OK;
 }
