@@ -603,6 +603,51 @@ int pfd_upscale_outlets(pfd_raster *h, int method, int64_t cellsize, int uparea_
                         const uint8_t *effarea_host, int idx_dtype, void *idxs_out_out, int memspace);
 int pfd_upscale_error(pfd_raster *h, int idx_dtype, const void *idxs_out, const void *idxs_ds_coarse, int64_t k,
                       uint8_t *out, int memspace);
+/* ---- windows along the flow path (csrc/window.hip) ---------------------------------------------------------------------
+ * The calls that look along the flow path around a cell.  D8 handles with 32-bit cell indices (a general idxs_ds handle, a
+ * row block and a raster beyond 2^32 - 2 cells return PFD_EUNSUPPORTED).  `memspace` covers every per-cell argument and
+ * the result.
+ * pfd_downstream — Flwdir.downstream (reference pyflwdir/flwdir.py:394-410): out[x] = data[idxs_ds[x]] for a valid cell (a
+ *   pit takes its own value), data[x] for a nodata cell.  A gather of elements of `elem_bytes` = 1, 2, 4 or 8 bytes: any
+ *   dtype of those sizes.
+ * pfd_moving_average — arithmetics.moving_average (arithmetics.py:67-103) over core._window (core.py:369-397): the window
+ *   of a cell is at most n cells down the downstream links (ending at a pit, and BEFORE a cell whose stream order is
+ *   greater than the CENTRE cell's when `strord` is given) and at most n cells up `idxs_us_main` (n indices of idx_dtype,
+ *   the dtype's -1 = none; every entry must drain into its cell, as pfd_main_upstream's do: PFD_EINVAL otherwise).  `strord`
+ *   (nullable): n values of strord_dtype (PFD_U8, PFD_I32, PFD_U32 or PFD_I64), compared as integers.  out = `nodata`
+ *   where data == nodata (compared in the data's dtype: a NaN nodata skips no cell); else arithmetics._average over the
+ *   window from its farthest upstream to its farthest downstream cell, skipping values == nodata (NaN nodata: isnan):
+ *   v += w0 * v0 in the common type of weights and data (the product rounded before the add), w += w0 in the type of the
+ *   weights, v / w rounded to the data's dtype, nodata where w == 0.  data PFD_F32 / PFD_F64; `weights` of weight_dtype
+ *   (PFD_F32 / PFD_F64), or NULL = float64 ones, as in the reference.  n >= 0; the walks are bounded by n, so a raster with
+ *   cycles is served like any other.
+ * pfd_moving_median — arithmetics.moving_median (arithmetics.py:106-143): the same window and cell test; np.nanmedian of
+ *   the window's values that are neither nodata nor NaN: the middle value, or (a + b) / 2 in the data's dtype for an even
+ *   count, NaN for none.  Values are ordered by the total order (-0.0 before 0.0; the reference's np.partition leaves the
+ *   order of zeros of both signs unspecified).  Windows of 2n + 1 <= WMAX cells (pfd_debug_window_wmax: 31 for float32, 15
+ *   for float64) are sorted in LDS, larger ones in a global workspace of a fixed byte budget that serves the raster in
+ *   chunks of cells: no n is refused for its size.
+ * pfd_path — core.path / core._trace (core.py:308-437; FlwdirRaster.path pyflwdir.py:443-500): per start cell (`idxs`, k
+ *   HOST int64) the cells of the walk along the downstream links (PFD_DOWN) or `idxs_us_main` (PFD_UP; n indices of
+ *   idx_dtype), the start cell included, up to and including the first cell where `mask` (uint8, nullable) is set, a pit,
+ *   a headwater or a missing link; with has_max_length the walk ends before the step that would make the distance exceed
+ *   max_length.  `step_lengths` as for pfd_snap (HOST table, NULL counts cells).  A CSR pair with the conventions of
+ *   pfd_streams: *n_out = M cells in all, always written; idxs_out (M cells of idx_dtype), offsets_out (k + 1 int64) and
+ *   dist_out (k float64, accumulated in float64 and NOT rounded to float32 as pfd_snap's are) are written only when
+ *   M <= cap_idxs (a sizing call passes cap_idxs = 0 and NULL lists).  A start index outside the raster and a walk that
+ *   does not end within n_cells steps (a cycle) return PFD_EINVAL.
+ * pfd_debug_window_wmax — *wmax = the largest window (2n + 1) the median sorts in LDS for `dtype` (PFD_F32 / PFD_F64). */
+int pfd_downstream(pfd_raster *h, int elem_bytes, const void *data, void *out, int memspace);
+int pfd_moving_average(pfd_raster *h, int64_t n, int idx_dtype, const void *idxs_us_main, int strord_dtype,
+                       const void *strord /* nullable */, int dtype, const void *data, int weight_dtype,
+                       const void *weights /* nullable */, double nodata, void *out, int memspace);
+int pfd_moving_median(pfd_raster *h, int64_t n, int idx_dtype, const void *idxs_us_main, int strord_dtype,
+                      const void *strord /* nullable */, int dtype, const void *data, double nodata, void *out, int memspace);
+int pfd_path(pfd_raster *h, const int64_t *idxs, int64_t k, int direction, int idx_dtype,
+             const void *idxs_us_main /* nullable for PFD_DOWN */, const uint8_t *mask /* nullable */,
+             const double *step_lengths /* nullable */, int has_max_length, double max_length, void *idxs_out,
+             int64_t cap_idxs, int64_t *offsets_out /* k + 1 */, double *dist_out /* k */, int64_t *n_out, int memspace);
+int pfd_debug_window_wmax(int dtype, int *wmax);
 /* dem.floodplains (reference pyflwdir/dem.py:333-379; FlwdirRaster.floodplains pyflwdir.py:1513-1545):
  * `is_stream` uint8 (1 where uparea >= upa_min), `stream_h` float32 (uparea ** b on those cells — evaluated by
  * the caller in the reference's dtype), elevtn PFD_F32 / PFD_F64; out int8: 1 floodplain, 0 not, -1 off the sequence. */

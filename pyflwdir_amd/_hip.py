@@ -27,6 +27,8 @@ UPSCALE_METHOD = {"dmm": 0, "eam": 1, "eam_plus": 2}  # PFD_UPSCALE_*
 _FLOAT_CODE = {np.dtype(np.float32): PFD_F32, np.dtype(np.float64): PFD_F64}
 
 IDX_CODE = {np.dtype(np.int32): PFD_I32, np.dtype(np.uint32): PFD_U32, np.dtype(np.int64): PFD_I64}
+# the stream order of the window calls (pfd_moving_average / pfd_moving_median)
+STRORD_CODE = {np.dtype(np.uint8): PFD_U8, np.dtype(np.int32): PFD_I32, np.dtype(np.uint32): PFD_U32, np.dtype(np.int64): PFD_I64}
 
 # status code -> Python exception (messages come from pfd_last_error()).  PFD_ENOPITS and
 # PFD_EBADCODE map to the ValueErrors the reference raises for the same conditions
@@ -54,6 +56,7 @@ SYMBOLS = [
     "pfd_interbasin_mask", "pfd_inflow_idxs", "pfd_basin_bounds", "pfd_subbasins_pfafstetter",
     "pfd_upscale", "pfd_upscale_outlets", "pfd_upscale_error",
     "pfd_ucat_volume", "pfd_segment_length", "pfd_segment_slope", "pfd_segment_average", "pfd_segment_median",
+    "pfd_downstream", "pfd_moving_average", "pfd_moving_median", "pfd_path", "pfd_debug_window_wmax",
 ]
 
 _lib = None
@@ -165,6 +168,14 @@ def lib() -> C.CDLL:
                                           C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int]
         L.pfd_segment_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_double, C.c_void_p, C.c_int]
+        L.pfd_downstream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.pfd_moving_average.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int]
+        L.pfd_moving_median.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_double, C.c_void_p, C.c_int]
+        L.pfd_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                               C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
+        L.pfd_debug_window_wmax.argtypes = [C.c_int, C.POINTER(C.c_int)]
         L.pfd_floodplains.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.pfd_snap_downstream.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         L.pfd_snap.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
@@ -289,6 +300,14 @@ def ensure_reserved(n_cells: int, device: int = 0):
         _auto_reserved[int(device)] = have + int(want)
     except (RuntimeError, MemoryError, ValueError):
         pass
+
+
+def window_wmax(dtype) -> int:
+    """The largest window (2n + 1 cells) ``moving_median`` sorts in LDS for float32 / float64 data; larger windows take
+    the global workspace (``pfd_debug_window_wmax``)."""
+    w = C.c_int(0)
+    check(lib().pfd_debug_window_wmax(_FLOAT_CODE[np.dtype(dtype)], C.byref(w)))
+    return int(w.value)
 
 
 def transfer_stats(reset: bool = True) -> dict:
@@ -757,6 +776,75 @@ class RasterHandle:
         check(lib().pfd_segment_median(self._h, ptr(idxs_out), idxs_out.size, int(direction), icode, ptr(us), ptr(mask), dcode,
                                        ptr(data), float(nodata), ptr(out), memspace))
         return out
+
+    # -- windows along the flow path (csrc/window.hip).  PFD_HOST: per-cell arguments are numpy arrays and the result is a
+    #    new array; PFD_DEVICE: they are DeviceBuffers — payloads as ``(DeviceBuffer, dtype code)`` pairs, ``idxs_us_main``
+    #    as ``(DeviceBuffer, numpy dtype)``, ``strord`` as ``(DeviceBuffer, STRORD code)`` — and ``out`` is returned.
+    def downstream(self, data, elem_bytes=None, out=None, memspace=PFD_HOST):
+        """data[idxs_ds] on valid cells, data elsewhere; elements of 1, 2, 4 or 8 bytes of any dtype."""
+        if memspace == PFD_HOST:
+            data = np.ascontiguousarray(data).ravel()
+            assert data.size == self.n
+            elem_bytes, out = data.dtype.itemsize, np.empty_like(data)
+        check(lib().pfd_downstream(self._h, int(elem_bytes), ptr(data), ptr(out), memspace))
+        return out
+
+    def _window_args(self, idxs_us_main, strord):
+        _, us, icode = self._segment_args((), idxs_us_main)
+        if strord is None:
+            return us, icode, None, 0
+        if isinstance(strord, tuple):
+            return us, icode, strord[0], int(strord[1])
+        strord = np.ascontiguousarray(strord).ravel()
+        assert strord.size == self.n
+        return us, icode, strord, STRORD_CODE[strord.dtype]
+
+    def moving_average(self, n, idxs_us_main, data, weights=None, strord=None, nodata=-9999.0, out=None, memspace=PFD_HOST):
+        """``weights`` None: float64 ones (the reference's default); ``strord`` uint8 / int32 / uint32 / int64 or None."""
+        us, icode, so, scode = self._window_args(idxs_us_main, strord)
+        data, dcode = _payload_pair(data)
+        weights, wcode = (None, PFD_F64) if weights is None else _payload_pair(weights)
+        if memspace == PFD_HOST:
+            out = np.empty(self.n, data.dtype)
+        check(lib().pfd_moving_average(self._h, int(n), icode, ptr(us), scode, ptr(so), dcode, ptr(data), wcode, ptr(weights),
+                                       float(nodata), ptr(out), memspace))
+        return out
+
+    def moving_median(self, n, idxs_us_main, data, strord=None, nodata=-9999.0, out=None, memspace=PFD_HOST):
+        us, icode, so, scode = self._window_args(idxs_us_main, strord)
+        data, dcode = _payload_pair(data)
+        if memspace == PFD_HOST:
+            out = np.empty(self.n, data.dtype)
+        check(lib().pfd_moving_median(self._h, int(n), icode, ptr(us), scode, ptr(so), dcode, ptr(data), float(nodata),
+                                      ptr(out), memspace))
+        return out
+
+    def path(self, idxs, direction, idx_dtype, idxs_us_main=None, mask=None, step_lengths=None, max_length=None,
+             idxs_out=None, offsets_out=None, dist_out=None, cap_idxs=None, memspace=PFD_HOST):
+        """The paths of pfd_path as a CSR pair plus distances: (cells[M] of ``idx_dtype``, offsets[k + 1] int64, float64
+        dists[k]).  PFD_DEVICE: ``idxs_us_main``, ``mask`` and the three lists (``cap_idxs`` cells; None with a cap of 0: a
+        sizing call) are DeviceBuffers; returns M, the lists are written when they fit."""
+        idxs = np.ascontiguousarray(idxs, dtype=np.int64).ravel()
+        k, m = idxs.size, C.c_int64(0)
+        code = IDX_CODE[np.dtype(idx_dtype)]
+        tab = None if step_lengths is None else np.ascontiguousarray(step_lengths, dtype=np.float64)
+        has_max, mx = (0, 0.0) if max_length is None else (1, float(max_length))
+        if isinstance(idxs_us_main, tuple):
+            idxs_us_main = idxs_us_main[0]
+
+        def run(cells, cap, offsets, dists, space):
+            check(lib().pfd_path(self._h, ptr(idxs), k, int(direction), code, ptr(idxs_us_main), ptr(mask), ptr(tab), has_max,
+                                 C.c_double(mx), ptr(cells), int(cap), ptr(offsets), ptr(dists), C.byref(m), space))
+        if memspace != PFD_HOST:
+            run(idxs_out, cap_idxs or 0, offsets_out, dist_out, memspace)
+            return int(m.value)
+        cap = max(4096, 64 * k)
+        while True:
+            cells, offsets, dists = np.empty(cap, idx_dtype), np.zeros(k + 1, np.int64), np.zeros(k, np.float64)
+            run(cells, cap, offsets, dists, PFD_HOST)
+            if m.value <= cap:
+                return cells[:m.value].copy(), offsets, dists
+            cap = int(m.value)
 
     # -- outlets derived from the network (csrc/outlets.hip) ------------------------------------------------------
     def _outlet_cap(self):

@@ -17,6 +17,8 @@ Mirrors (names, argument meaning, return conventions, error messages):
                                        reference pyflwdir/pyflwdir.py:631-663, :694-718, :742-766, :804-818
 * ``vectorize`` / ``streams`` / ``geofeatures`` reference pyflwdir/pyflwdir.py:865-892, :894-974, :976-1009
 * ``hand``                             reference pyflwdir/pyflwdir.py:1485-1511
+* ``downstream`` / ``moving_average`` / ``moving_median`` / ``path``
+                                       reference pyflwdir/flwdir.py:394-410, :435-504, pyflwdir/pyflwdir.py:443-500
 * ``add_pits`` / ``order_cells``       reference pyflwdir/flwdir.py:231-279, pyflwdir/pyflwdir.py:299-315
 * ``_check_data`` / ``_check_idxs_xy`` reference pyflwdir/flwdir.py:782-811, pyflwdir/pyflwdir.py:1548-1566
 
@@ -26,6 +28,7 @@ There is no CPU fallback: without the HIP library or a device the methods raise.
 """
 from __future__ import annotations
 
+import operator
 import os
 import pickle
 
@@ -1399,6 +1402,97 @@ class FlwdirRaster(object):
         rivmed = self._h.segment_median(idx64, _hip.PFD_DOWN if direction == "down" else _hip.PFD_UP, self._subgrid_us(direction),
                                         self._subgrid_mask(mask), data, nodata)
         return rivmed.reshape(idxs_out.shape)
+
+    # -- windows along the flow path (csrc/window.hip: one lane per cell and a bounded walk) ----------------
+    def downstream(self, data):
+        """The value of the next downstream cell: ``out = data.copy(); out[mask] = data[idxs_ds[mask]]`` — a pit takes
+        its own value, a nodata flow cell keeps its own; reference pyflwdir/flwdir.py:394-410.  A gather of 1-, 2-, 4- or
+        8-byte elements: every numpy dtype of those sizes, ``bool`` included; dtype and shape of ``data``."""
+        self._subgrid_refusals("downstream", walks=False)
+        flat = self._check_data(data, "data")
+        if flat.dtype.kind not in "biufcmM" or flat.dtype.itemsize not in (1, 2, 4, 8):
+            raise NotImplementedError(f"downstream: data dtype {flat.dtype} is not supported on the HIP path "
+                                      "(plain elements of 1, 2, 4 or 8 bytes)")
+        out = self._h.downstream(np.ascontiguousarray(flat))
+        return out.reshape(np.shape(data) if np.size(data) == self.size else self.shape)
+
+    def _window_inputs(self, what, data, n, restrict_strord, strord):
+        """(data, n, idxs_us_main, stream order or None) of a window call, after the refusals that come before any
+        kernel.  The stream-order rule is in force when ``strord`` is given OR ``restrict_strord`` is true."""
+        self._subgrid_refusals(what, walks=False)  # (the walks are bounded by n: a loop is served like the reference does)
+        data = self._subgrid_float(data, "data", what)
+        try:
+            if isinstance(n, (bool, np.bool_)):
+                raise TypeError
+            n = operator.index(n)
+        except TypeError:
+            raise ValueError(f"{what}: n must be a non-negative integer, not {n!r}") from None
+        if n < 0:
+            raise ValueError(f"{what}: n must be a non-negative integer, not {n!r}")
+        strord = self._check_data(strord, "strord", optional=not restrict_strord)
+        if strord is not None:
+            if strord.dtype.kind not in "iu" or strord.dtype == np.uint64:
+                raise NotImplementedError(f"{what}: strord dtype {strord.dtype} is not supported on the HIP path "
+                                          "(an integer stream order, compared as integers)")
+            if strord.dtype not in _hip.STRORD_CODE:  # (int8 / int16 / uint16 widen exactly)
+                strord = strord.astype(np.int64)
+            strord = np.ascontiguousarray(strord)
+        return data, n, np.ascontiguousarray(self.idxs_us_main), strord
+
+    def moving_average(self, data, n, weights=None, restrict_strord=False, strord=None, nodata=-9999.0):
+        """Moving weighted average over the flow direction network: per cell the window of at most ``n`` cells down the
+        flow path and ``n`` cells up the main upstream cells, cells equal to ``nodata`` skipped (a NaN ``nodata``: NaN
+        values); ``nodata`` where ``data`` is nodata or the weights sum to 0; reference pyflwdir/flwdir.py:435-470 +
+        pyflwdir/arithmetics.py:67-103.  ``data`` and ``weights`` are float32 or float64; the sums run from the farthest
+        upstream to the farthest downstream cell in the types of the reference's loop (float64 without weights).
+        With a stream order the window ends downstream BEFORE a cell of a higher order than the centre cell.  As in the
+        reference, a given ``strord`` is in force even with ``restrict_strord=False``; ``restrict_strord=True`` without
+        ``strord`` uses ``self.stream_order()``."""
+        what = "moving_average"
+        if weights is not None:
+            weights = self._subgrid_float(weights, "weights", what)
+        flat, n, us, strord = self._window_inputs(what, data, n, restrict_strord, strord)
+        out = self._h.moving_average(n, us, flat, weights, strord, nodata)
+        return out.reshape(np.shape(data) if np.size(data) == self.size else self.shape)
+
+    def moving_median(self, data, n, restrict_strord=False, strord=None, nodata=-9999.0):
+        """Moving median over the window of ``moving_average``: ``np.nanmedian`` of the window's values that are neither
+        ``nodata`` nor NaN — the mean of the two middle values in the data's dtype for an even count, NaN for a window
+        without values; reference pyflwdir/flwdir.py:472-504 + pyflwdir/arithmetics.py:106-143.  The stream-order
+        arguments act as in ``moving_average`` (a given ``strord`` is in force even with ``restrict_strord=False``).
+        Zeros of both signs in one window: the reference's ``np.partition`` leaves their order unspecified; here
+        ``-0.0`` sorts before ``0.0``."""
+        what = "moving_median"
+        flat, n, us, strord = self._window_inputs(what, data, n, restrict_strord, strord)
+        out = self._h.moving_median(n, us, flat, strord, nodata)
+        return out.reshape(np.shape(data) if np.size(data) == self.size else self.shape)
+
+    def path(self, idxs=None, xy=None, mask=None, max_length=None, unit="cell", direction="down"):
+        """Paths of cell indices down- or upstream (along the main upstream cells) from the start cells, each up to and
+        including a pit / headwater or the first cell where ``mask`` is True, or ending before the step that would exceed
+        ``max_length``; returns (list of 1D index arrays, float64 distances); reference pyflwdir/pyflwdir.py:443-500 +
+        core.path / core._trace (pyflwdir/core.py:308-437).  One count walk and one fill walk per start cell on the
+        device; the list holds views of one flat array."""
+        unit = str(unit).lower()
+        if unit not in ["m", "cell"]:
+            raise ValueError(f'Unknown unit: {unit}, select from ["m", "cell"].')
+        direction = str(direction).lower()
+        if direction not in ["up", "down"]:
+            raise ValueError('Unknown flow direction: {direction}, select from ["up", "down"].')
+        self._subgrid_refusals("path", walks=False)
+        if self._has_loop():
+            raise ValueError("path: the flow direction raster holds a loop; a path that enters it would never end")
+        idxs0 = np.asarray(self._check_idxs_xy(idxs, xy))
+        if idxs0.dtype.kind not in "iu":
+            raise IndexError("path: start cells must be integer linear indices")
+        if idxs0.size and (int(idxs0.min()) < 0 or int(idxs0.max()) >= self.size):
+            raise IndexError("idxs outside domain")
+        m = self._subgrid_mask(mask)
+        us = np.ascontiguousarray(self.idxs_us_main) if direction == "up" else None
+        tab = gis.step_length_table(self.shape[0], self.latlon, self.transform, dtype=np.float64) if unit == "m" else None
+        cells, offsets, dists = self._h.path(idxs0, _hip.PFD_UP if direction == "up" else _hip.PFD_DOWN, self._idx_dtype,
+                                             idxs_us_main=us, mask=m, step_lengths=tab, max_length=max_length)
+        return [cells[offsets[i]:offsets[i + 1]] for i in range(idxs0.size)], dists
 
     # -- upscaling (csrc/upscale.hip: a per-coarse-cell arg-max and per-coarse-cell walks, DESIGN.md) ------------------
     def _has_loop(self):
