@@ -549,6 +549,31 @@ int pfd_basin_bounds(pfd_raster *h, int dtype, const void *labels, void *lbs_out
 int pfd_subbasins_pfafstetter(pfd_raster *h, int dtype, const void *uparea, double upa_min, int depth,
                               const int64_t *idxs_us_main, const int64_t *idxs_pit, int64_t npits, int idx_dtype,
                               void *idxs_out, int64_t cap, int64_t *k_out, int32_t *map_out, int memspace);
+/* ---- sub-basins of a minimum area (csrc/subbasins_area.hip) ----------------------------------------------------------
+ * pfd_subbasins_area — basins.subbasins_area (basins.py:194-233; FlwdirRaster.subbasins_area pyflwdir.py:665-692).  Moving
+ *   upstream from the pits, a tributary whose area exceeds area_min where what is left of the main stem's area also does
+ *   becomes an outlet, and so does a main-stem cell once the area between it and the cell below exceeds area_min.
+ *   `uparea`: n values of `dtype` (PFD_I32 / PFD_I64 / PFD_F32 / PFD_F64) or NULL = the upstream cell count (int32).  Every
+ *   difference of areas is formed and rounded in that dtype; `compare` says where `> area_min` is evaluated:
+ *   PFD_COMPARE_OWN in the areas' dtype, area_min rounded to it once (integer areas: area_min must be one of its values,
+ *   PFD_EINVAL otherwise), PFD_COMPARE_F64 in float64.  A NaN area is above nothing.  `idxs_us_main`: n int64 (-1 = none)
+ *   or NULL = the main upstream cells by upstream cell count; every entry must be another cell that drains into its cell,
+ *   and a cell at which a tributary becomes an outlet must have one (PFD_EINVAL otherwise).
+ *   idxs_out: the outlets in sequence order, the pits first — list conventions of pfd_outflow_idxs (`cap`; *k_out is always
+ *   written, the list only when it fits).  map_out: n uint32, the list position + 1 of the first outlet on the cell's
+ *   downstream path, itself included; 0 off the sequence (nodata, and cells on or above a loop: a raster with loops is
+ *   served).  stats_out (nullable): [0] mode 0 = pruned (the cells above area_min are closed downstream: a cell that is
+ *   not above it is never followed) / 1 = full, [1] rounds, [2] jobs, [3] lane steps (groups run).  flags:
+ *   PFD_SUBAREA_FULL forces the full mode (same result; for tests).  `memspace` covers uparea, idxs_us_main, map_out and
+ *   the list.  PFD_EUNSUPPORTED beyond 2^32 - 2 cells, on row-block handles and on general idxs_ds handles: the only
+ *   sequence of a general graph is the reference's np.argsort by rank, an unstable sort, so the order of the upstream
+ *   cells of one cell — on which this result depends — is unspecified there. */
+#define PFD_COMPARE_OWN 0
+#define PFD_COMPARE_F64 1
+#define PFD_SUBAREA_FULL 1
+int pfd_subbasins_area(pfd_raster *h, int dtype, const void *uparea /* nullable */, double area_min, int compare,
+                       const int64_t *idxs_us_main /* nullable */, int idx_dtype, void *idxs_out, int64_t cap,
+                       int64_t *k_out, uint32_t *map_out, int64_t *stats_out /* nullable, 4 */, int flags, int memspace);
 /* ---- stream segments: from outlet lists to segment lists (csrc/streams.hip) ----------------------------------------
  * pfd_streams — streams.streams (reference pyflwdir/streams.py:132-188; FlwdirRaster.streams pyflwdir.py:894-974) as a
  *   CSR triple.  `mask` uint8 (!= 0: stream cell; NULL: every cell).  With nup = the upstream count inside the mask, a

@@ -23,6 +23,8 @@ PFD_UP, PFD_DOWN, PFD_BOTH = 0, 1, 2  # (PFD_BOTH: pfd_segment_slope only)
 PFD_U64, PFD_I8, PFD_U8, PFD_I16, PFD_U16 = 6, 7, 8, 9, 10
 PFD_FILL_MAX, PFD_FILL_MIN, PFD_FILL_SUM = 0, 1, 2
 UPSCALE_METHOD = {"dmm": 0, "eam": 1, "eam_plus": 2}  # PFD_UPSCALE_*
+PFD_COMPARE_OWN, PFD_COMPARE_F64 = 0, 1  # pfd_subbasins_area: where `> area_min` is evaluated
+PFD_SUBAREA_FULL = 1  # pfd_subbasins_area flag: follow every cell (tests)
 
 _FLOAT_CODE = {np.dtype(np.float32): PFD_F32, np.dtype(np.float64): PFD_F64}
 
@@ -54,6 +56,7 @@ SYMBOLS = [
     "pfd_subbasins_streamorder", "pfd_outflow_idxs", "pfd_basin_outlets",
     "pfd_streams",
     "pfd_interbasin_mask", "pfd_inflow_idxs", "pfd_basin_bounds", "pfd_subbasins_pfafstetter",
+    "pfd_subbasins_area",
     "pfd_upscale", "pfd_upscale_outlets", "pfd_upscale_error",
     "pfd_ucat_volume", "pfd_segment_length", "pfd_segment_slope", "pfd_segment_average", "pfd_segment_median",
     "pfd_downstream", "pfd_moving_average", "pfd_moving_median", "pfd_path", "pfd_debug_window_wmax",
@@ -133,6 +136,8 @@ def lib() -> C.CDLL:
         L.pfd_subbasins_pfafstetter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
                                                 C.c_int]
+        L.pfd_subbasins_area.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.pfd_upscale.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_int]
         L.pfd_upscale_outlets.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -939,6 +944,30 @@ class RasterHandle:
                                                   ptr(idxs), cap, C.byref(k), ptr(out), PFD_HOST))
             if k.value <= cap:
                 return out, idxs[:k.value].copy()
+            cap = int(k.value)
+
+    def subbasins_area(self, uparea, dtype_code, area_min, compare, idxs_us_main, idx_dtype, cap=None, flags=0, out=None,
+                       idxs_out=None, memspace=PFD_HOST):
+        """(uint32 map[n], outlet cells[k], int64 stats[4] = mode, rounds, jobs, lane steps) of pfd_subbasins_area;
+        ``uparea`` / ``idxs_us_main`` (int64) may be None.  PFD_DEVICE: ``uparea``, ``idxs_us_main``, ``out`` and ``idxs_out``
+        (``cap`` entries) are DeviceBuffers; returns (out, idxs_out, k, stats)."""
+        k = C.c_int64(0)
+        stats = np.zeros(4, np.int64)
+        icode = IDX_CODE[np.dtype(idx_dtype)]
+        if memspace != PFD_HOST:
+            check(lib().pfd_subbasins_area(self._h, int(dtype_code), ptr(uparea), float(area_min), int(compare),
+                                           ptr(idxs_us_main), icode, ptr(idxs_out), int(cap), C.byref(k), ptr(out), ptr(stats),
+                                           int(flags), memspace))
+            return out, idxs_out, int(k.value), stats
+        out = np.empty(self.n, np.uint32)
+        cap = self._outlet_cap() if cap is None else int(cap)
+        while True:
+            idxs = np.empty(cap, idx_dtype)
+            check(lib().pfd_subbasins_area(self._h, int(dtype_code), ptr(uparea), float(area_min), int(compare),
+                                           ptr(idxs_us_main), icode, ptr(idxs), cap, C.byref(k), ptr(out), ptr(stats),
+                                           int(flags), PFD_HOST))
+            if k.value <= cap:
+                return out, idxs[:k.value].copy(), stats
             cap = int(k.value)
 
     # -- upscaling (csrc/upscale.hip) ------------------------------------------------------------------------------------

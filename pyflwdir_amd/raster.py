@@ -15,6 +15,7 @@ Mirrors (names, argument meaning, return conventions, error messages):
 * ``basin_outlets`` / ``outflow_idxs`` reference pyflwdir/pyflwdir.py:720-740, :820-835
 * ``subbasins_pfafstetter`` / ``basin_bounds`` / ``interbasin_mask`` / ``inflow_idxs``
                                        reference pyflwdir/pyflwdir.py:631-663, :694-718, :742-766, :804-818
+* ``subbasins_area``                   reference pyflwdir/pyflwdir.py:665-692
 * ``vectorize`` / ``streams`` / ``geofeatures`` reference pyflwdir/pyflwdir.py:865-892, :894-974, :976-1009
 * ``hand``                             reference pyflwdir/pyflwdir.py:1485-1511
 * ``downstream`` / ``moving_average`` / ``moving_median`` / ``path``
@@ -63,6 +64,28 @@ _D8_TO_LDD[D8_DS.ravel()] = LDD_DS.ravel()
 
 _PAYLOAD = {np.dtype(np.int32): _hip.PFD_I32, np.dtype(np.int64): _hip.PFD_I64,
             np.dtype(np.float32): _hip.PFD_F32, np.dtype(np.float64): _hip.PFD_F64}
+
+
+def _area_min_compare(dtype, area_min):
+    """(area_min as a float, PFD_COMPARE_*) for ``scalar of dtype > area_min`` as numpy >= 2 evaluates it (NEP 50): a
+    Python number is weak — compared in a float dtype itself, an integer dtype against a float in float64 —, a numpy
+    scalar or 0-d array is strong: the comparison is made in the common type."""
+    dtype = np.dtype(dtype)
+    if isinstance(area_min, (bool, int, float)) and not isinstance(area_min, np.generic):
+        if dtype.kind == "f":
+            return float(area_min), _hip.PFD_COMPARE_OWN
+        info = np.iinfo(dtype)
+        own = not isinstance(area_min, float) and max(info.min, -2**53) <= area_min <= min(info.max, 2**53)
+        return float(area_min), _hip.PFD_COMPARE_OWN if own else _hip.PFD_COMPARE_F64
+    am = np.asarray(area_min)
+    if am.ndim != 0 or am.dtype.kind not in "biuf":
+        raise ValueError("area_min must be a real scalar")
+    common = np.result_type(dtype, am.dtype)
+    if common == dtype:
+        return float(am), _hip.PFD_COMPARE_OWN
+    if common == np.float64 or common.kind in "iu":  # (integers: exact in float64 below 2**53)
+        return float(am), _hip.PFD_COMPARE_F64
+    raise NotImplementedError(f"subbasins_area: comparing {dtype} areas with a {am.dtype} area_min in {common}")
 
 
 _INFER_ON_DEVICE_MIN = 1 << 24  # cells from which ftype="infer" asks the device whether a uint8 raster is D8
@@ -999,6 +1022,39 @@ class FlwdirRaster(object):
             us = cached.astype(np.int64)
             us[cached == self._mv] = -1
         subbas, idxs_out = self._h.subbasins_pfafstetter(upa, code, upa_min, depth, us, self.idxs_pit, self._idx_dtype)
+        return subbas.reshape(self.shape), idxs_out
+
+    def subbasins_area(self, area_min, uparea=None):
+        """Sub-basin map (uint32 ids, 0 = none) with a minimum area of ``area_min`` and the linear indices of the outlets
+        (id = list position + 1); reference pyflwdir/pyflwdir.py:665-692, basins.py:194-233.  Moving upstream from the
+        pits, a new sub-basin starts at a tributary whose area exceeds ``area_min`` while the rest of the main stem's
+        does too, and a new inter-basin where the main stem has lost more than ``area_min`` to tributaries.  ``uparea``
+        defaults to ``upstream_area("km2")``; int32, int64, float32 and float64 areas are taken as they are — the dtype
+        decides the arithmetic, so nothing is converted — and ``area_min`` is compared as numpy compares it with a
+        scalar of that dtype (a Python number in the areas' float dtype, a numpy scalar in the common type).  The main
+        stems follow ``idxs_us_main``: the cached array if there is one, whatever area chose it.
+
+        The reference's loop over ``idxs_seq`` runs on the device as one short serial loop per parent cell (csrc/
+        subbasins_area.hip).  A raster with loops is served: cells on or above a loop read 0.  Not available on a general
+        ``idxs_ds`` graph (the order of the upstream cells of one cell, on which the result depends, is unspecified in
+        its sequence) and beyond 2**32 - 2 cells."""
+        if self._d8 is None:
+            raise NotImplementedError("subbasins_area is not available on a general idxs_ds graph on the HIP path: the "
+                                      "order of the upstream cells of one cell is unspecified in its sequence")
+        if self._row_blocks_needed() > 1:
+            raise NotImplementedError("subbasins_area is limited to rasters of at most 2**32 - 2 cells")
+        upa = self._check_data(uparea, "uparea", unit="km2")
+        if upa.dtype not in _PAYLOAD:
+            raise NotImplementedError(f"subbasins_area: uparea dtype {upa.dtype} is not supported on the HIP path "
+                                      "(int32, int64, float32, float64: the dtype decides the arithmetic)")
+        area_min, compare = _area_min_compare(upa.dtype, area_min)
+        us = None
+        if self.cache or "idxs_us_main" in self._cached:
+            cached = self.idxs_us_main
+            us = cached.astype(np.int64)
+            us[cached == self._mv] = -1
+        subbas, idxs_out, _ = self._h.subbasins_area(np.ascontiguousarray(upa), _PAYLOAD[upa.dtype], area_min, compare, us,
+                                                     self._idx_dtype)
         return subbas.reshape(self.shape), idxs_out
 
     # -- stream segments (csrc/streams.hip: flags, list of starts in sequence order, two walks) ----------------------
