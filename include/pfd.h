@@ -230,14 +230,14 @@ int pfd_fillnodata(pfd_raster *h, int dtype, const void *data, int64_t nodata_i,
 /* OPT-IN, tolerance mode of FlwdirRaster.upstream_area(unit != "cell") on lat/lon grids (reference
  * pyflwdir/pyflwdir.py:770-801: a float64 accumulation of cell areas): `row_values` is a HOST pointer to nrow float64
  * areas, `out` receives n float64 sums, -9999 on nodata cells.  The areas are quantised to 64-bit fixed point (the
- * largest power-of-two scale that keeps the raster's total below 2^64; *quantum, if given, receives one unit of it) and
+ * largest power-of-two scale that keeps the raster's rounded float64 total below 2^63, one bit of headroom; *quantum, if given, receives one unit of it) and
  * accumulated as integers on the LDS-tiled engine of pfd_upstream_area_cell (a cell gets the integer part of its row's
  * scaled area plus its Bresenham share of the fraction, so that any run of consecutive cells of a row is off by less than
  * one quantum): the result does not depend on any execution order, every value is the exact sum of the quantised areas,
- * |error| < upstream cells x quantum in the worst case (relative: <= n_cells / 2^63 x mean / min area, 1.3e-10 at
+ * |error| < upstream cells x quantum in the worst case (relative: <= n_cells / 2^62 x mean / min area, 2.6e-10 at
  * 30000^2, reached at cells with a handful of upstream cells) plus one float64 rounding — NOT bit-identical to the reference's
  * serial float64 sum (pfd_accuflux_rows is).  *used = 0: not taken (cycles, row block, general graph, a value that is not
- * finite and positive, a supertile the 64-bit LDS form cannot hold); `out` is then undefined, call pfd_accuflux_rows. */
+ * finite and positive or lies below the quantum, a total below 2^-960 whose scale is no finite float64, a supertile the 64-bit LDS form cannot hold); `out` is then undefined, call pfd_accuflux_rows. */
 int pfd_upstream_area_rows_fixed(pfd_raster *h, const double *row_values, double *out, int memspace, int *used,
                                  double *quantum);
 /* streams.strahler_order (reference pyflwdir/streams.py:228-269); mask uint8 or NULL. */

@@ -4,14 +4,15 @@
 // pyflwdir/pyflwdir.py:770-801 + streams.accuflux, streams.py:15-41).  Float addition is not associative, so the exact
 // (default) form folds every sum in the order of the reference's serial loop (exact.hip: a plan of 44 ms at 30000^2
 // and a sweep of 17 ms).  This file is the OPT-IN alternative (`exact=False` in the front end): the areas are
-// quantised once to 64-bit fixed point — area[r] * 2^s, s the largest power that keeps the sum over the whole raster
-// below 2^64; a cell gets the integer part plus its share of the fraction (w_cell: Bresenham along the row, so that
+// quantised once to 64-bit fixed point — area[r] * 2^s, s the largest power that keeps the (rounded float64) sum over the
+// whole raster below 2^63: one bit of headroom, so that a total which rounds across a power of two cannot reach 2^64;
+// a cell gets the integer part plus its share of the fraction (w_cell: Bresenham along the row, so that
 // any run of consecutive cells of a row is off by less than one unit) — and accumulated as INTEGERS on the LDS-tiled pointer-doubling engine of this file's
 // includer.  Integer addition is associative: the result is the same in any execution order (run to run, tile order,
 // and it would be across row blocks), every cell's value is the exact sum of the quantised areas of its upstream
 // cells, and what separates it from the real-number sum is the quantisation alone:
-//     |result - sum| < (row runs in the upstream set) * 2^-s  <=  N_up(x) * 2^-s,   2^-s <= (sum of all areas) / 2^63
-// i.e. relative <= n_cells / 2^63 * mean / min area: 1.3e-10 at 30000^2, 6e-10 at 2^32 cells, reached at cells with a
+//     |result - sum| < (row runs in the upstream set) * 2^-s  <=  N_up(x) * 2^-s,   2^-s <= (sum of all areas) / 2^62
+// i.e. relative <= n_cells / 2^62 * mean / min area: 2.6e-10 at 30000^2, 1.2e-9 at 2^32 cells, reached at cells with a
 // handful of upstream cells (one quantum against one cell's area); a large basin is off by far less (measured:
 // see profiles/r06f_wide_probe.txt) plus one float64 rounding of the final value.  The reference's own serial float64 sum carries up to N * 2^-53
 // relative error (1e-7 worst case at 9e8 terms, ~3e-12 typical) — the two agree far inside the north star's 1e-6.
@@ -595,9 +596,14 @@ extern "C" int pfd_upstream_area_rows_fixed(pfd_raster *h, const double *row_val
   tot *= (double)h->ncol;
   if (!(tot > 0.0) || !(tot < 1e300)) return PFD_OK;
   int ex = 0;
-  (void)frexp(tot, &ex);          // tot = f * 2^ex, f in [0.5, 1)  =>  tot * 2^(64 - ex) in [2^63, 2^64): unsigned sums cannot wrap
-  const int s = 64 - ex;          // (a row of cells sums to ncol * base + floor(ncol * fraction) <= ncol * area * 2^s)
+  (void)frexp(tot, &ex);          // tot = f * 2^ex, f in [0.5, 1)  =>  tot * 2^(63 - ex) in [2^62, 2^63)
+  // `tot` is a ROUNDED float64 sum: the real total may lie on the other side of 2^ex (ten rows of 0.1 x 64 columns:
+  // tot = 63.99999999999999, the quantised weights sum to 64 * 2^s + 1024).  One bit of headroom keeps the unsigned sums
+  // from wrapping: the real total is below tot * (1 + nrow * 2^-52) < 2^(ex + 1).
+  const int s = 63 - ex;          // (a row of cells sums to ncol * base + floor(ncol * fraction) <= ncol * area * 2^s)
+  if (s > 1023 || s < -1022) return PFD_OK;  // (2^s is no finite normal float64: a total below 2^-960)
   const double scale = ldexp(1.0, s), inv = ldexp(1.0, -s);
+  if (!(scale > 0.0) || !(scale < HUGE_VAL) || !(inv > 0.0) || !(inv < HUGE_VAL)) return PFD_OK;  // (before any integer conversion)
   // per row: floor(area * 2^s) and the fraction left over, as a 32-bit fixed-point number the columns share out (w_cell)
   std::vector<u64> q((size_t)h->nrow);
   std::vector<u32> qf((size_t)h->nrow);

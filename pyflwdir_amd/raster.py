@@ -620,7 +620,7 @@ class FlwdirRaster(object):
         ``exact`` (not in the reference; default True = bit-identical to its serial sums).  ``exact=False`` is an
         opt-in tolerance mode for the float64 sums of lat/lon grids only: the row areas are quantised to 64-bit fixed
         point and accumulated as integers on the tiled engine of ``unit="cell"`` (csrc/wide.h) — independent of any
-        execution order, within n_cells / 2**63 relative of the real-number sum (1.3e-10 at 30000 x 30000), and several
+        execution order, within n_cells / 2**62 relative of the real-number sum (2.6e-10 at 30000 x 30000), and several
         times faster on a fresh raster because it needs no ordering plan.  It is never offered for float32 sums
         (projected grids): a sequential float32 sum drifts from the real-number sum by more than the 1e-6 this path
         promises, so only the exact order reproduces it.  Whatever the fast form cannot take (cycles, general graphs) is

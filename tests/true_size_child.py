@@ -45,7 +45,7 @@ def main():
     flw = pyflwdir.from_array(d8, ftype="d8", transform=Affine(res, 0.0, 5.0, 0.0, -res, 60.0), latlon=True, cache=False)
     assert flw._wide() and flw.idxs_pit.dtype == np.int64
     # upstream_area in km2, order-free in fixed point (csrc/wide.h) on ONE handle of 4.36e9 cells, against the exact form in
-    # seeded row blocks on sampled rows: within the stated n_cells / 2**63 x (mean / min area) relative, and the local
+    # seeded row blocks on sampled rows: within the stated n_cells / 2**62 x (mean / min area) relative, and the local
     # equation area(x) = own + sum of the upstream cells' areas to the same tolerance
     t0 = time.perf_counter()
     fx = flw.upstream_area("km2", exact=False)
