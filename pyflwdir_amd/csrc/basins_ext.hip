@@ -1,6 +1,7 @@
 // basins_ext.hip — the rest of the reference's BASINS section: basins.interbasin_mask (reference pyflwdir/basins.py:25-64),
 // core.inflow_idxs (core.py:485-497), regions.region_bounds (regions.py:57-125) and basins.subbasins_pfafstetter
-// (basins.py:106-191).  The serial loops are restated in closed form ("The rest of BASINS"):
+// (basins.py:106-191).  The serial loops are restated in closed form ("The rest of BASINS"); the argument check
+// of the list calls, the handle's links and sequence, the compaction and the list kernels are those of lists.h:
 //   interbasin_mask   the second loop never reads the first loop's mask off a pit, so the result is: inside the region,
 //                     the pit's basin holds a stream cell, and no edge "outside -> inside" on the path down to the pit.
 //                     Two label fills (pfd_basins_dev): basin numbers (which pits have a stream cell), then the pits and
@@ -182,12 +183,6 @@ __global__ void __launch_bounds__(256) k_inflow_walk(const D d, const I *__restr
     if (found) atomicAdd(count, (ull)found);
   }
 }
-template <class I>
-__global__ void __launch_bounds__(256) k_reverse_i64(const I *__restrict__ sel, u64 k, i64 *__restrict__ idx) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i < k) idx[i] = (i64)sel[k - 1 - i];
-}
-
 template <class D, class I>
 static int inflow_run(pfd_raster *h, const D &d, const I *seq, u64 m, const u8 *region, DevBuf &idx, u64 *k_out) {
   const u64 n = (u64)h->n;
@@ -218,7 +213,7 @@ static int inflow_run(pfd_raster *h, const D &d, const I *seq, u64 m, const u8 *
   PFDCHK(idx.alloc((size_t)marked * sizeof(i64)));
   pfd_seg_begin(h, "inflow_list");
   PFDCHK(select_marked(h, seq, m, mark.as<u8>(), sel.as<I>(), c + 1));
-  k_reverse_i64<I><<<cdiv_u32(marked, 256), 256, 0, h->stream>>>(sel.as<I>(), marked, idx.as<i64>());
+  k_number<I><<<cdiv_u32(marked, 256), 256, 0, h->stream>>>(sel.as<I>(), marked, true, idx.as<i64>(), nullptr);
   KCHK();
   pfd_seg_end(h, 2);
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -242,12 +237,6 @@ __global__ void __launch_bounds__(256) k_run_starts(const T *__restrict__ v, u64
     const u64 b = __ballot(m);
     if ((threadIdx.x & 63u) == 0 && b) atomicAdd(count, (ull)__popcll(b));
   }
-}
-template <class T>
-__global__ void __launch_bounds__(256) k_gather_labels(const i64 *__restrict__ idx, u64 k, const T *__restrict__ v,
-                                                       T *__restrict__ out) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i < k) out[i] = v[idx[i]];
 }
 // bounds = [rmin[k], rmax[k], cmin[k], cmax[k]]; only the two ends of a run touch them
 template <class T>
@@ -295,17 +284,15 @@ static int bounds_t(pfd_raster *h, const void *labels, void *lbs_out, i64 *bound
   PFDCHK(uq.alloc((size_t)ns * sizeof(T)));
   pfd_seg_begin(h, "bounds_labels");
   PFDCHK(select_marked(h, rocprim::counting_iterator<i64>(0), n, mark.as<u8>(), starts.as<i64>(), c + 1));
-  k_gather_labels<T><<<cdiv_u32(ns, 256), 256, 0, h->stream>>>(starts.as<i64>(), ns, (const T *)v.dev, lb.as<T>());
+  k_gather<T><<<cdiv_u32(ns, 256), 256, 0, h->stream>>>(starts.as<i64>(), ns, (const T *)v.dev, lb.as<T>());
   KCHK();
-  size_t tb = 0;
-  HIPCHK(rocprim::radix_sort_keys(nullptr, tb, lb.as<T>(), lb2.as<T>(), (size_t)ns, 0u, (unsigned)(8 * sizeof(T)), h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::radix_sort_keys(tmp.p, tb, lb.as<T>(), lb2.as<T>(), (size_t)ns, 0u, (unsigned)(8 * sizeof(T)), h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::radix_sort_keys(p, b, lb.as<T>(), lb2.as<T>(), (size_t)ns, 0u, (unsigned)(8 * sizeof(T)), h->stream);
+  }));
   HIPCHK(hipStreamSynchronize(h->stream));
-  tb = 0;
-  HIPCHK(rocprim::unique(nullptr, tb, lb2.as<T>(), uq.as<T>(), c + 2, (size_t)ns, rocprim::equal_to<T>(), h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::unique(tmp.p, tb, lb2.as<T>(), uq.as<T>(), c + 2, (size_t)ns, rocprim::equal_to<T>(), h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::unique(p, b, lb2.as<T>(), uq.as<T>(), c + 2, (size_t)ns, rocprim::equal_to<T>(), h->stream);
+  }));
   pfd_seg_end(h, 4);
   u64 k = 0;
   PFDCHK(read_count(h, c + 2, &k));
@@ -640,7 +627,7 @@ static int pfaf_run(pfd_raster *h, const D &d, const I *seq, u64 m, const T *upa
     PFDCHK(sidx.alloc((size_t)ks * sizeof(i64)));
     PFDCHK(sids.alloc((size_t)ks * sizeof(i32)));
     PFDCHK(select_marked(h, rocprim::counting_iterator<i64>(0), (u64)n, mark.as<u8>(), sidx.as<i64>(), c + 3));
-    k_gather_labels<i32><<<cdiv_u32(ks, 256), 256, 0, h->stream>>>(sidx.as<i64>(), ks, branch.as<i32>(), sids.as<i32>());
+    k_gather<i32><<<cdiv_u32(ks, 256), 256, 0, h->stream>>>(sidx.as<i64>(), ks, branch.as<i32>(), sids.as<i32>());
     KCHK();
   }
   PFDCHK(pfd_basins_dev(h, sidx.as<i64>(), sids.p, (u32)ks, 4, out));
@@ -716,26 +703,6 @@ static int pfaf_t(pfd_raster *h, const void *uparea, double upa_min, int depth, 
   return o.finish(h->stream);
 }
 
-static int check_list_args(pfd_raster *h, const char *what, const void *data, int idx_dtype, const void *list_out, i64 cap,
-                           const i64 *k_out) {
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_require_unblocked(h, what));
-  if (!data || !k_out || cap < 0 || (cap > 0 && !list_out)) {
-    pfd_set_error("%s: bad arguments (NULL pointer, cap=%lld)", what, (long long)cap);
-    return PFD_EINVAL;
-  }
-  if (!pfd_idx_bytes(idx_dtype)) {
-    pfd_set_error("%s: unsupported index dtype code %d", what, idx_dtype);
-    return PFD_EUNSUPPORTED;
-  }
-  if (h->n > 4294967294ll && idx_dtype != PFD_I64) {
-    pfd_set_error("%s of a raster of %lld cells needs the int64 index dtype (PFD_I64)", what, (long long)h->n);
-    return PFD_EINVAL;
-  }
-  pfd_seg_clear(h);
-  return PFD_OK;
-}
-
 }  // namespace
 
 extern "C" int pfd_interbasin_mask(pfd_raster *h, const uint8_t *region, const uint8_t *stream, uint8_t *out, int memspace) {
@@ -752,21 +719,13 @@ extern "C" int pfd_interbasin_mask(pfd_raster *h, const uint8_t *region, const u
   OutArg o;
   PFDCHK(o.bind(out, (size_t)h->n, memspace));
   // (order-independent: the links alone, no sequence)
-  if (h->gen) {
-    const u32 *ds = nullptr, *seq = nullptr;
-    PFDCHK(pfd_gen_graph_dev(h, &ds, &seq));
-    PFDCHK(interbasin_run(h, DownGen{ds}, (const u8 *)r.dev, (const u8 *)s.dev, (u8 *)o.dev));
-  } else if (pfd_wide_cells(h)) {
-    PFDCHK(interbasin_run(h, DownWide{h->ncode, h->ncol}, (const u8 *)r.dev, (const u8 *)s.dev, (u8 *)o.dev));
-  } else {
-    PFDCHK(interbasin_run(h, DownD8{h->ncode, h->geo}, (const u8 *)r.dev, (const u8 *)s.dev, (u8 *)o.dev));
-  }
+  PFDCHK(pfd_with_links(h, [&](auto d) { return interbasin_run(h, d, (const u8 *)r.dev, (const u8 *)s.dev, (u8 *)o.dev); }));
   return o.finish(h->stream);
 }
 
 extern "C" int pfd_inflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dtype, void *idxs_out, int64_t cap,
                                int64_t *k_out, int memspace) {
-  PFDCHK(check_list_args(h, "inflow_idxs", region, idx_dtype, idxs_out, cap, k_out));
+  PFDCHK(pfd_check_list_args(h, "inflow_idxs", region, idx_dtype, idxs_out, cap, k_out));
   InArg r;
   PFDCHK(r.bind(region, (size_t)h->n, memspace, h->stream));
   DevBuf idx;
@@ -802,7 +761,7 @@ extern "C" int pfd_basin_bounds(pfd_raster *h, int dtype, const void *labels, vo
 extern "C" int pfd_subbasins_pfafstetter(pfd_raster *h, int dtype, const void *uparea, double upa_min, int depth,
                                          const int64_t *idxs_us_main, const int64_t *idxs_pit, int64_t npits, int idx_dtype,
                                          void *idxs_out, int64_t cap, int64_t *k_out, int32_t *map_out, int memspace) {
-  PFDCHK(check_list_args(h, "subbasins_pfafstetter", map_out, idx_dtype, idxs_out, cap, k_out));
+  PFDCHK(pfd_check_list_args(h, "subbasins_pfafstetter", map_out, idx_dtype, idxs_out, cap, k_out));
   if (pfd_wide_cells(h)) {
     pfd_set_error("subbasins_pfafstetter: pfd_main_upstream and pfd_stream_order_classic have no one-handle form beyond "
                   "2^32 - 2 cells (%lld cells)", (long long)h->n);

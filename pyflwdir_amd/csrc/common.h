@@ -325,6 +325,12 @@ template <class T>
 static inline T pfd_nodata_as(int64_t nodata_i, double nodata_f) {
   return std::is_floating_point<T>::value ? (T)nodata_f : (T)nodata_i;
 }
+static inline bool is_float_code(int c) { return c == PFD_F32 || c == PFD_F64; }
+// numpy's promotion of two float types: float64 if either is
+template <class A, class B>
+struct Wider {
+  typedef typename std::conditional<std::is_same<A, double>::value || std::is_same<B, double>::value, double, float>::type type;
+};
 template <class F>
 static int pfd_dispatch_payload(int dtype, const char *what, F f) {
   switch (dtype) {

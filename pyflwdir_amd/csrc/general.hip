@@ -8,7 +8,7 @@
 // downstream index per cell, an upstream CSR (stable radix sort of the edges by target: upstream cells in
 // ascending index), the exact breadth-first order of core.idxs_seq (core.py:87-117) built level by level
 // (count / scan / scatter), and pull sweeps with one launch per level — children combined in descending
-// index, the serial loop's order, so float results are bit-identical here too.
+// index, the serial loop's order, so float results are bit-identical here too.  (rocprim scratch: pfd_rocprim, lists.h.)
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "fill.h"
+#include "lists.h"
 #include "rules.h"
 
 int pfd_export_u32(pfd_raster *h, const u32 *src, i64 m, int idx_dtype, void *out, int memspace);  // api.hip
@@ -148,10 +149,9 @@ static int gen_build_csr(pfd_raster *h) {
     PFDCHK(order.alloc((size_t)n * sizeof(u32)));
     PFDCHK(flag.alloc(((size_t)n + 1) * sizeof(u32)));
     k_gen_notin<<<cdiv_u32(n + 1, 256), 256, 0, h->stream>>>(g->pos, n, flag.as<u32>());
-    size_t tb0 = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb0, flag.as<u32>(), flag.as<u32>(), 0u, (size_t)n + 1, rocprim::plus<u32>(), h->stream));
-    PFDCHK(tmp0.alloc(std::max<size_t>(tb0, 16)));
-    HIPCHK(rocprim::exclusive_scan(tmp0.p, tb0, flag.as<u32>(), flag.as<u32>(), 0u, (size_t)n + 1, rocprim::plus<u32>(), h->stream));
+    PFDCHK(pfd_rocprim(tmp0, [&](void *p, size_t &b) {
+      return rocprim::exclusive_scan(p, b, flag.as<u32>(), flag.as<u32>(), 0u, (size_t)n + 1, rocprim::plus<u32>(), h->stream);
+    }));
     k_gen_rest<<<cdiv_u32(n, 256), 256, 0, h->stream>>>(g->pos, n, (u32)h->n_seq, flag.as<u32>(), order.as<u32>());
   }
   k_gen_edges<<<cdiv_u32(n, 256), 256, 0, h->stream>>>(g->ds, n, g->pos ? order.as<u32>() : nullptr, keys.as<u32>(),
@@ -159,15 +159,13 @@ static int gen_build_csr(pfd_raster *h) {
   KCHK();
   int bits = 1;
   while ((1ull << bits) <= (u64)n) ++bits;
-  size_t tb = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys.as<u32>(), keys2.as<u32>(), vals.as<u32>(), g->cidx, (size_t)n, 0u,
-                                   (unsigned)bits, h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::radix_sort_pairs(tmp.p, tb, keys.as<u32>(), keys2.as<u32>(), vals.as<u32>(), g->cidx, (size_t)n, 0u,
-                                   (unsigned)bits, h->stream));
-  HIPCHK(rocprim::exclusive_scan(nullptr, tb, g->coff, g->coff, 0u, (size_t)n + 1, rocprim::plus<u32>(), h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::exclusive_scan(tmp.p, tb, g->coff, g->coff, 0u, (size_t)n + 1, rocprim::plus<u32>(), h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::radix_sort_pairs(p, b, keys.as<u32>(), keys2.as<u32>(), vals.as<u32>(), g->cidx, (size_t)n, 0u, (unsigned)bits,
+                                     h->stream);
+  }));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::exclusive_scan(p, b, g->coff, g->coff, 0u, (size_t)n + 1, rocprim::plus<u32>(), h->stream);
+  }));
   HIPCHK(hipStreamSynchronize(h->stream));
   g->csr_ready = true;
   return PFD_OK;
@@ -283,10 +281,9 @@ static int gen_order(pfd_raster *h) {
       PFDCHK(deg.alloc(cap * sizeof(u32)));
     }
     k_gen_deg<<<cdiv_u32(m + 1, 256), 256, 0, h->stream>>>(g->seq, begin, end, g->coff, deg.as<u32>());
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, deg.as<u32>(), deg.as<u32>(), 0u, (size_t)m + 1, rocprim::plus<u32>(), h->stream));
-    PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-    HIPCHK(rocprim::exclusive_scan(tmp.p, tb, deg.as<u32>(), deg.as<u32>(), 0u, (size_t)m + 1, rocprim::plus<u32>(), h->stream));
+    PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+      return rocprim::exclusive_scan(p, b, deg.as<u32>(), deg.as<u32>(), 0u, (size_t)m + 1, rocprim::plus<u32>(), h->stream);
+    }));
     u32 total = 0;
     HIPCHK(hipMemcpyAsync(&total, deg.as<u32>() + m, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

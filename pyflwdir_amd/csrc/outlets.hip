@@ -11,8 +11,8 @@
 // outflow_idxs has one more step: its `mask`, inherited from the downstream cell and cleared at every listed cell, says
 // "no listed cell further down the path" — and since the lowest candidate of a path is always listed, that is "no
 // CANDIDATE further down": one label fill of the candidate flags, then every candidate looks at its downstream cell.
-// The sequence comes from the engine the handle already has — pfd_exact_seq_dev (32-bit cells), the 64-bit queue of
-// order64.hip, the (installed) order of a general graph — and never leaves the device.
+// The sequence comes from the engine the handle already has (pfd_with_graph, lists.h) and never leaves the device; the
+// argument check, the compaction and the list kernels are those of lists.h.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -69,20 +69,6 @@ __global__ void __launch_bounds__(256) k_drop_shadowed(const D d, u64 n, const u
     if ((threadIdx.x & 63u) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
   }
 }
-// the list as the reference appends it (reversed: the loops over seq[::-1]) in 64-bit indices, and its numbers 1..k
-template <class I>
-__global__ void __launch_bounds__(256) k_number(const I *__restrict__ sel, u64 k, bool reversed, i64 *__restrict__ idx,
-                                                u32 *__restrict__ ids) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i >= k) return;
-  idx[i] = (i64)sel[reversed ? k - 1 - i : i];
-  ids[i] = (u32)(i + 1);
-}
-template <class T>
-__global__ void __launch_bounds__(256) k_gather(const i64 *__restrict__ idx, u64 k, const T *__restrict__ v, T *__restrict__ out) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i < k) out[i] = v[idx[i]];
-}
 struct Outlets {  // the numbered list on the device
   DevBuf idx, ids;  // k x i64 cells in the reference's list order, k x u32 numbers 1..k
   u64 k = 0;
@@ -138,45 +124,6 @@ static int outlets_run(pfd_raster *h, const D &d, const I *seq, u64 m, const T *
   return PFD_OK;
 }
 
-// the handle's own sequence and downstream links
-template <int RULE, class T>
-static int outlets_of(pfd_raster *h, const T *v, i64 min_sto, bool reversed, Outlets &R) {
-  if (h->gen) {
-    const u32 *ds = nullptr, *seq = nullptr;
-    PFDCHK(pfd_gen_graph_dev(h, &ds, &seq));
-    return outlets_run<RULE, T>(h, DownGen{ds}, seq, (u64)h->n_seq, v, min_sto, reversed, R);
-  }
-  if (pfd_wide_cells(h)) {
-    DevBuf q;
-    u64 nseq = 0;
-    PFDCHK(pfd_wide_seq_dev(h, q, &nseq));
-    return outlets_run<RULE, T>(h, DownWide{h->ncode, h->ncol}, (const u64 *)q.p, nseq, v, min_sto, reversed, R);
-  }
-  DevBuf oseq;
-  PFDCHK(pfd_exact_seq_dev(h, oseq));
-  return outlets_run<RULE, T>(h, DownD8{h->ncode, h->geo}, (const u32 *)oseq.p, (u64)h->n_seq, v, min_sto, reversed, R);
-}
-
-static int check_common(pfd_raster *h, const char *what, const void *data, int idx_dtype, const void *idxs_out, i64 cap,
-                        const i64 *k_out) {
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_require_unblocked(h, what));
-  if (!data || !k_out || cap < 0 || (cap > 0 && !idxs_out)) {
-    pfd_set_error("%s: bad arguments (NULL pointer, cap=%lld)", what, (long long)cap);
-    return PFD_EINVAL;
-  }
-  if (!pfd_idx_bytes(idx_dtype)) {
-    pfd_set_error("%s: unsupported index dtype code %d", what, idx_dtype);
-    return PFD_EUNSUPPORTED;
-  }
-  if (h->n > 4294967294ll && idx_dtype != PFD_I64) {
-    pfd_set_error("%s of a raster of %lld cells needs the int64 index dtype (PFD_I64)", what, (long long)h->n);
-    return PFD_EINVAL;
-  }
-  pfd_seg_clear(h);
-  return PFD_OK;
-}
-
 template <class T>
 static int streamorder_t(pfd_raster *h, const void *strord, i64 min_sto, int idx_dtype, void *idxs_out, i64 cap, i64 *k_out,
                          i32 *map_out, int memspace) {
@@ -185,7 +132,7 @@ static int streamorder_t(pfd_raster *h, const void *strord, i64 min_sto, int idx
   OutArg o;
   PFDCHK(o.bind(map_out, (size_t)h->n * sizeof(i32), memspace));
   Outlets R;
-  PFDCHK((outlets_of<R_STO, T>(h, (const T *)v.dev, min_sto, true, R)));
+  PFDCHK(pfd_with_graph(h, [&](auto d, auto seq, u64 m) { return outlets_run<R_STO, T>(h, d, seq, m, (const T *)v.dev, min_sto, true, R); }));
   if (R.k > 0x7FFFFFFFull) {
     pfd_set_error("subbasins_streamorder: %llu outlets do not fit the int32 map", (unsigned long long)R.k);
     return PFD_EUNSUPPORTED;
@@ -202,7 +149,7 @@ static int basin_outlets_t(pfd_raster *h, const void *regions, int idx_dtype, vo
   InArg v;
   PFDCHK(v.bind(regions, (size_t)h->n * sizeof(T), memspace, h->stream));
   Outlets R;
-  PFDCHK((outlets_of<R_LABEL, T>(h, (const T *)v.dev, 0, true, R)));
+  PFDCHK(pfd_with_graph(h, [&](auto d, auto seq, u64 m) { return outlets_run<R_LABEL, T>(h, d, seq, m, (const T *)v.dev, 0, true, R); }));
   *k_out = (i64)R.k;
   if (!R.k || (i64)R.k > cap) return PFD_OK;
   // by label, stable: the outlets of one label stay in reversed sequence order
@@ -214,12 +161,10 @@ static int basin_outlets_t(pfd_raster *h, const void *regions, int idx_dtype, vo
   pfd_seg_begin(h, "outlets_sort");
   k_gather<T><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(R.idx.as<i64>(), k, (const T *)v.dev, lb.as<T>());
   KCHK();
-  size_t tb = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, lb.as<T>(), lb2.as<T>(), R.idx.as<i64>(), idx2.as<i64>(), (size_t)k, 0u,
-                                   (unsigned)(8 * sizeof(T)), h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::radix_sort_pairs(tmp.p, tb, lb.as<T>(), lb2.as<T>(), R.idx.as<i64>(), idx2.as<i64>(), (size_t)k, 0u,
-                                   (unsigned)(8 * sizeof(T)), h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::radix_sort_pairs(p, b, lb.as<T>(), lb2.as<T>(), R.idx.as<i64>(), idx2.as<i64>(), (size_t)k, 0u,
+                                     (unsigned)(8 * sizeof(T)), h->stream);
+  }));
   pfd_seg_end(h, 2);
   PFDCHK(give_list(h, lb2.p, (size_t)k * sizeof(T), lbs_out, memspace));
   return give_idxs(h, idx2.as<i64>(), k, idx_dtype, idxs_out, memspace);
@@ -229,7 +174,7 @@ static int basin_outlets_t(pfd_raster *h, const void *regions, int idx_dtype, vo
 
 extern "C" int pfd_subbasins_streamorder(pfd_raster *h, int dtype, const void *strord, int64_t min_sto, int idx_dtype,
                                          void *idxs_out, int64_t cap, int64_t *k_out, int32_t *map_out, int memspace) {
-  PFDCHK(check_common(h, "subbasins_streamorder", strord, idx_dtype, idxs_out, cap, k_out));
+  PFDCHK(pfd_check_list_args(h, "subbasins_streamorder", strord, idx_dtype, idxs_out, cap, k_out));
   if (!map_out) {
     pfd_set_error("subbasins_streamorder: NULL map_out");
     return PFD_EINVAL;
@@ -247,11 +192,11 @@ extern "C" int pfd_subbasins_streamorder(pfd_raster *h, int dtype, const void *s
 
 extern "C" int pfd_outflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dtype, void *idxs_out, int64_t cap,
                                 int64_t *k_out, int memspace) {
-  PFDCHK(check_common(h, "outflow_idxs", region, idx_dtype, idxs_out, cap, k_out));
+  PFDCHK(pfd_check_list_args(h, "outflow_idxs", region, idx_dtype, idxs_out, cap, k_out));
   InArg v;
   PFDCHK(v.bind(region, (size_t)h->n, memspace, h->stream));
   Outlets R;
-  PFDCHK((outlets_of<R_REGION, u8>(h, (const u8 *)v.dev, 0, false, R)));
+  PFDCHK(pfd_with_graph(h, [&](auto d, auto seq, u64 m) { return outlets_run<R_REGION, u8>(h, d, seq, m, (const u8 *)v.dev, 0, false, R); }));
   *k_out = (i64)R.k;
   if ((i64)R.k <= cap) PFDCHK(give_idxs(h, R.idx.as<i64>(), R.k, idx_dtype, idxs_out, memspace));
   return PFD_OK;
@@ -259,7 +204,7 @@ extern "C" int pfd_outflow_idxs(pfd_raster *h, const uint8_t *region, int idx_dt
 
 extern "C" int pfd_basin_outlets(pfd_raster *h, int dtype, const void *regions, int idx_dtype, void *idxs_out, void *lbs_out,
                                  int64_t cap, int64_t *k_out, int memspace) {
-  PFDCHK(check_common(h, "basin_outlets", regions, idx_dtype, idxs_out, cap, k_out));
+  PFDCHK(pfd_check_list_args(h, "basin_outlets", regions, idx_dtype, idxs_out, cap, k_out));
   if (cap > 0 && !lbs_out) {
     pfd_set_error("basin_outlets: NULL lbs_out");
     return PFD_EINVAL;

@@ -18,12 +18,10 @@
 //            in the sequence and never start a segment, and no walk from a sequence cell reaches them;
 //   measure  one thread per segment walks from its start, one flag byte per step: length, ended-in-a-pit;
 //   offsets  exclusive scan of the lengths;
-//   fill     the same walk again, writing the cells at the segment's offset.
+//   fill     the same walk again, writing the cells at the segment's offset
+//            (these three, the room check and the hand-over are pfd_ragged_tail of lists.h, given the two walks).
 // The `[p, p]` entries after a segment that ends in a pit and the max_len pieces are O(segments) slicing of this triple
 // and stay with the caller (pyflwdir_amd/raster.py).
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-
 #include <algorithm>
 
 #include "common.h"
@@ -108,16 +106,6 @@ __global__ void __launch_bounds__(256) k_walk(const D d, const u32 *__restrict__
   if (!FILL) len[j] = l, pit[j] = p ? 1 : 0;
 }
 
-// no segment at all: the offsets are the single 0 (when the caller gave room for offsets)
-static int give_empty(pfd_raster *h, i64 *offsets_out, int memspace) {
-  if (offsets_out) {
-    if (memspace == PFD_DEVICE) HIPCHK(hipMemsetAsync(offsets_out, 0, sizeof(i64), h->stream));
-    else offsets_out[0] = 0;
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return PFD_OK;
-}
-
 template <class D>
 static int streams_run(pfd_raster *h, const D &d, const u32 *seq, u64 m, const u8 *mask, const int8_t *nup, int idx_dtype,
                        void *idxs_out, i64 cap_idxs, i64 *offsets_out, u8 *pit_out, i64 cap_segs, i64 *n_out, int memspace) {
@@ -164,58 +152,37 @@ static int streams_run(pfd_raster *h, const D &d, const u32 *seq, u64 m, const u
   DevBuf sel, tmp;
   PFDCHK(sel.alloc((size_t)starts * sizeof(u32)));
   pfd_seg_begin(h, "streams_list");
-  size_t tb = 0;
-  HIPCHK(rocprim::select(nullptr, tb, seq, sel.as<u32>(), c + 2, (size_t)m, IsStart{flag.as<u8>()}, h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::select(tmp.p, tb, seq, sel.as<u32>(), c + 2, (size_t)m, IsStart{flag.as<u8>()}, h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::select(p, b, seq, sel.as<u32>(), c + 2, (size_t)m, IsStart{flag.as<u8>()}, h->stream);
+  }));
   pfd_seg_end(h, 1);
   HIPCHK(hipMemcpyAsync(&kk, c + 2, sizeof(kk), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   const u64 k = (u64)kk;
-  if (!k) return give_empty(h, offsets_out, memspace);
-  DevBuf off, pit, tmp2;
-  PFDCHK(off.alloc((size_t)(k + 1) * sizeof(i64)));
-  PFDCHK(pit.alloc((size_t)k));
-  pfd_seg_begin(h, "streams_walk_measure");
-  HIPCHK(hipMemsetAsync(off.as<i64>() + k, 0, sizeof(i64), h->stream));
-  k_walk<false, D, i32><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(d, sel.as<u32>(), k, flag.as<u8>(), off.as<i64>(), pit.as<u8>(),
-                                                                nullptr, nullptr);
-  KCHK();
-  pfd_seg_end(h, 1);
-  pfd_seg_begin(h, "streams_offsets");
-  tb = 0;
-  HIPCHK(rocprim::exclusive_scan(nullptr, tb, off.as<i64>(), off.as<i64>(), (i64)0, (size_t)(k + 1), rocprim::plus<i64>(),
-                                 h->stream));
-  PFDCHK(tmp2.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::exclusive_scan(tmp2.p, tb, off.as<i64>(), off.as<i64>(), (i64)0, (size_t)(k + 1), rocprim::plus<i64>(),
-                                 h->stream));
-  pfd_seg_end(h, 1);
+  DevBuf pit;
+  PFDCHK(pit.alloc(std::max<size_t>((size_t)k, 1)));
+  const u32 wgrid = cdiv_u32(k, 256);
+  const RaggedSegs segs = {"streams_walk_measure", "streams_offsets", "streams_walk_fill", "streams indices"};
+  const RaggedOut ro = {idx_dtype, idxs_out, cap_idxs, offsets_out, cap_segs, memspace};
   i64 total = 0;
-  HIPCHK(hipMemcpyAsync(&total, off.as<i64>() + k, sizeof(total), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  bool given = false;
+  PFDCHK(pfd_ragged_tail(
+      h, segs, k, ro,
+      [&](i64 *len) -> int {
+        k_walk<false, D, i32><<<wgrid, 256, 0, h->stream>>>(d, sel.as<u32>(), k, flag.as<u8>(), len, pit.as<u8>(), nullptr, nullptr);
+        KCHK();
+        return PFD_OK;
+      },
+      [] { return PFD_OK; },  // (no error word: a walk from a cell of the sequence ends at a pit)
+      [&](auto itag, const i64 *off, auto *dst) -> int {
+        typedef typename decltype(itag)::type I;
+        k_walk<true, D, I><<<wgrid, 256, 0, h->stream>>>(d, sel.as<u32>(), k, flag.as<u8>(), nullptr, nullptr, off, dst);
+        KCHK();
+        return PFD_OK;
+      },
+      &total, &given));
   n_out[0] = (i64)k, n_out[1] = total;
-  if ((i64)k > cap_segs || total > cap_idxs) return PFD_OK;
-  const int rc = pfd_dispatch_idx(idx_dtype, "streams indices", [&](auto itag) -> int {
-    typedef typename decltype(itag)::type I;
-    DevBuf stage;
-    I *dst = (I *)idxs_out;
-    if (memspace != PFD_DEVICE) {
-      PFDCHK(stage.alloc((size_t)total * sizeof(I)));
-      dst = stage.as<I>();
-    }
-    pfd_seg_begin(h, "streams_walk_fill");
-    k_walk<true, D, I><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(d, sel.as<u32>(), k, flag.as<u8>(), nullptr, nullptr,
-                                                               off.as<i64>(), dst);
-    KCHK();
-    pfd_seg_end(h, 1);
-    if (memspace != PFD_DEVICE) PFDCHK(give_list(h, stage.p, (size_t)total * sizeof(I), idxs_out, memspace));
-    else HIPCHK(hipStreamSynchronize(h->stream));
-    return PFD_OK;
-  });
-  PFDCHK(rc);
-  PFDCHK(give_list(h, off.p, (size_t)(k + 1) * sizeof(i64), offsets_out, memspace));
-  PFDCHK(give_list(h, pit.p, (size_t)k, pit_out, memspace));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  if (given) PFDCHK(give_list(h, pit.p, (size_t)k, pit_out, memspace));
   return PFD_OK;
 }
 
@@ -247,14 +214,12 @@ extern "C" int pfd_streams(pfd_raster *h, const uint8_t *mask, int idx_dtype, vo
   pfd_seg_begin(h, "streams_nup");
   PFDCHK(pfd_upstream_count(h, (const u8 *)mk.dev, nup.as<int8_t>(), PFD_DEVICE));
   pfd_seg_end(h, 1);
-  if (h->gen) {
-    const u32 *ds = nullptr, *seq = nullptr;
-    PFDCHK(pfd_gen_graph_dev(h, &ds, &seq));
-    return streams_run(h, DownGen{ds}, seq, (u64)h->n_seq, (const u8 *)mk.dev, nup.as<int8_t>(), idx_dtype, idxs_out, cap_idxs,
-                       offsets_out, pit_out, cap_segs, n_out, memspace);
-  }
-  DevBuf oseq;
-  PFDCHK(pfd_exact_seq_dev(h, oseq));
-  return streams_run(h, DownD8{h->ncode, h->geo}, (const u32 *)oseq.p, (u64)h->n_seq, (const u8 *)mk.dev, nup.as<int8_t>(),
-                     idx_dtype, idxs_out, cap_idxs, offsets_out, pit_out, cap_segs, n_out, memspace);
+  // (a raster with 64-bit cells was refused above: the sequence is one of 32-bit cells)
+  return pfd_with_graph(h, [&](auto d, auto seq, u64 m) -> int {
+    if constexpr (std::is_same<decltype(seq), const u32 *>::value)
+      return streams_run(h, d, seq, m, (const u8 *)mk.dev, nup.as<int8_t>(), idx_dtype, idxs_out, cap_idxs, offsets_out, pit_out,
+                         cap_segs, n_out, memspace);
+    else
+      return PFD_EUNSUPPORTED;
+  });
 }

@@ -4,7 +4,7 @@
 // "subbasins_area"): while the children of p are visited the loop reads upa_out[p] only, and writes upa_out[p] and
 // upa_out[child of p] only.  A group is a serial loop over at most 8 children in ascending linear index; what it hands
 // to the groups of its children is one number per child; no order between groups matters.
-//   import     idxs_us_main into 32-bit lanes, every entry checked to be another cell that drains into its cell
+//   import     idxs_us_main into 32-bit lanes under the strict rule of walks.h: another, valid cell that drains into its cell
 //   scan       the pits (outlets, and the jobs of round 0); whether {area > area_min} is closed downstream: then a child
 //              outside it can neither be nor lead to an outlet and is not followed (PRUNED mode; else FULL mode); the
 //              number of cells a round can queue, which sizes the job lists
@@ -13,7 +13,8 @@
 //              upstream cell itself.  With the default main upstream cells (largest upstream cell count) a queued child
 //              holds at most half of its parent's cells: at most log2(n_seq) + 1 rounds.
 //   list, map  the stable compaction of the exact sequence by the marks; the label fill of pfd_basins with ids 1 .. k
-// The walks are latency-bound gathers with one lane per job, like the other walks of this library.
+// The walks are latency-bound gathers with one lane per job, like the other walks of this library; the error word, the
+// import kernel and the list kernels are the shared ones of walks.h / lists.h.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -25,8 +26,8 @@ namespace {
 
 typedef unsigned long long ull;
 
-enum { SA_CAP = 1, SA_INPUT = 2, SA_INVERSE = 4, SA_NOMAIN = 8, SA_LIST = 16 };
-#define SA_MV 0xFFFFFFFFu
+enum { SA_NOMAIN = WE_OWN, SA_LIST = WE_OWN << 1 };  // the call's own bits of the error word (walks.h)
+const WalkErrText SA_TEXT = {"an index of idxs_us_main", "a walk did not end within n_cells steps"};
 
 // x > area_min, in the areas' own type (F64 = false: `thr` is area_min rounded to it) or in float64
 template <class T, bool F64>
@@ -44,23 +45,6 @@ __device__ __forceinline__ T sa_sub(T a, T b) {
   } else {
     return a - b;
   }
-}
-
-__global__ void __launch_bounds__(256) k_sa_import(const i64 *__restrict__ in, u32 n, const DownD8 d, u32 *__restrict__ out,
-                                                   u32 *__restrict__ err) {
-  const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (j >= n) return;
-  const i64 v = in[j];
-  u32 o = SA_MV;
-  if (v != -1) {
-    if (v < 0 || v >= (i64)n) {
-      atomicOr(err, (u32)SA_INPUT);
-    } else {
-      o = (u32)v;
-      if ((u64)o == j || !d.valid(o) || d.down(o) != j) atomicOr(err, (u32)SA_INVERSE);
-    }
-  }
-  out[j] = o;
 }
 
 // mark = the pits; count[0] = valid non-pit cells above area_min that drain to a cell not above it, count[1] / [2] = the
@@ -148,7 +132,7 @@ __global__ void __launch_bounds__(256) k_sa_walk(const DownD8 d, const T *__rest
             v = u;
             up = sa_sub(up, u);
             um = up, um_set = true;
-            if (m == SA_MV) atomicOr(err, (u32)SA_NOMAIN);
+            if (m == PFD_NOCELL) atomicOr(err, (u32)SA_NOMAIN);
           }
           if (full || ab(u)) qm |= 1u << s, vq[s] = v;
         }
@@ -156,7 +140,7 @@ __global__ void __launch_bounds__(256) k_sa_walk(const DownD8 d, const T *__rest
       if (saw_m && (full || ab(am))) p = m, up = um;
       else live = false;
       if (live && steps > d.g.n) {
-        atomicOr(err, (u32)SA_CAP);
+        atomicOr(err, (u32)WE_CAP);
         live = false;
       }
     }
@@ -191,32 +175,16 @@ __global__ void __launch_bounds__(256) k_sa_walk(const DownD8 d, const T *__rest
   if (lane == 0 && found) atomicAdd(ctr + 2, (ull)found);
 }
 
-__global__ void __launch_bounds__(256) k_sa_widen(const u32 *__restrict__ sel, u64 k, i64 *__restrict__ idx, u32 *__restrict__ ids) {
-  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (i < k) idx[i] = (i64)sel[i], ids[i] = (u32)(i + 1);
-}
-
-static int sa_read_err(pfd_raster *h, const u32 *dev) {
-  u32 e = 0;
-  HIPCHK(hipMemcpyAsync(&e, dev, sizeof(e), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (e & SA_INPUT) {
-    pfd_set_error("subbasins_area: an index of idxs_us_main lies outside the raster");
-    return PFD_EINVAL;
-  }
-  if (e & SA_INVERSE) {
-    pfd_set_error("subbasins_area: idxs_us_main holds a cell that does not drain into the cell it is listed for");
-    return PFD_EINVAL;
-  }
-  if (e & SA_NOMAIN) {
+// the shared findings of the error word, then the call's own.  (WE_CAP cannot be set beside SA_NOMAIN: a walk follows
+// decoded upstream neighbours only, which never lead back to a cell.)
+static int sa_check_err(pfd_raster *h, WalkErr &err) {
+  u32 own = 0;
+  PFDCHK(err.check(h, "subbasins_area", SA_TEXT, &own));
+  if (own & SA_NOMAIN) {
     pfd_set_error("subbasins_area: idxs_us_main has no main upstream cell where a tributary above area_min joins");
     return PFD_EINVAL;
   }
-  if (e & SA_CAP) {
-    pfd_set_error("subbasins_area: a walk did not end within n_cells steps");
-    return PFD_EINVAL;
-  }
-  if (e & SA_LIST) {
+  if (own & SA_LIST) {
     pfd_set_error("subbasins_area: a round queued more jobs than there are cells to follow");
     return PFD_EINVAL;
   }
@@ -225,7 +193,7 @@ static int sa_read_err(pfd_raster *h, const u32 *dev) {
 
 // the marks of the outlets and their number; stats = mode, rounds, jobs, lane steps
 template <class T, bool F64>
-static int sa_rounds(pfd_raster *h, const T *A, const u32 *usm, double area_min, int flags, u8 *mark, u32 *err, u64 *marked,
+static int sa_rounds(pfd_raster *h, const T *A, const u32 *usm, double area_min, int flags, u8 *mark, WalkErr &err, u64 *marked,
                      i64 stats[4]) {
   const DownD8 d{h->ncode, h->geo};
   const u64 n = (u64)h->n;
@@ -263,7 +231,7 @@ static int sa_rounds(pfd_raster *h, const T *A, const u32 *usm, double area_min,
     const int q = (int)(rounds & 1);
     HIPCHK(hipMemsetAsync(c, 0, sizeof(ull), h->stream));
     k_sa_walk<T, F64><<<cdiv_u32(nj, 256), 256, 0, h->stream>>>(d, A, usm, ab, full, cur, cur_vals, (u32)nj, jobs[q].as<u32>(),
-                                                                 vals[q].as<T>(), (u32)cap, mark, c, err);
+                                                                 vals[q].as<T>(), (u32)cap, mark, c, err.dev());
     KCHK();
     ++launches, ++rounds, total += (i64)nj;
     u64 nn = 0;
@@ -272,7 +240,7 @@ static int sa_rounds(pfd_raster *h, const T *A, const u32 *usm, double area_min,
     cur = jobs[q].as<u32>(), cur_vals = vals[q].as<T>(), nj = nn;
   }
   pfd_seg_end(h, launches);
-  PFDCHK(sa_read_err(h, err));
+  PFDCHK(sa_check_err(h, err));
   u64 lane_steps = 0, found = 0;
   PFDCHK(read_count(h, c + 1, &lane_steps));
   PFDCHK(read_count(h, c + 2, &found));
@@ -295,33 +263,31 @@ static int sa_t(pfd_raster *h, const void *uparea, double area_min, int compare,
   PFDCHK(u.bind(idxs_us_main, (size_t)n * sizeof(i64), memspace, h->stream));
   OutArg o;
   PFDCHK(o.bind(map_out, (size_t)n * sizeof(u32), memspace));
-  DevBuf cells, usm, err, mark, oseq, cnt, sel, idx, ids;
+  DevBuf cells, usm, mark, oseq, cnt, sel, idx, ids;
+  WalkErr err;
   const T *upa = (const T *)a.dev;
   PFDCHK(usm.alloc((size_t)n * sizeof(u32)));
   if (!upa || !u.dev) {  // the upstream cell count: the default area, and what the main upstream cell is chosen by
     PFDCHK(cells.alloc((size_t)n * sizeof(i32)));
     PFDCHK(pfd_upstream_area_cell(h, cells.as<i32>(), PFD_DEVICE));
   }
-  if (!u.dev) PFDCHK(pfd_main_upstream(h, PFD_I32, cells.p, 0.0, PFD_U32, usm.p, PFD_DEVICE));  // (none: all-ones = SA_MV)
+  if (!u.dev) PFDCHK(pfd_main_upstream(h, PFD_I32, cells.p, 0.0, PFD_U32, usm.p, PFD_DEVICE));  // (none: all-ones = PFD_NOCELL)
   if (!upa) upa = (const T *)cells.p;  // (T is int32 then)
   pfd_seg_clear(h);
-  PFDCHK(err.alloc(sizeof(u32)));
-  HIPCHK(hipMemsetAsync(err.p, 0, sizeof(u32), h->stream));
+  PFDCHK(err.init(h));
   if (u.dev) {
     pfd_seg_begin(h, "subarea_import");
-    k_sa_import<<<cdiv_u32((u64)n, 256), 256, 0, h->stream>>>((const i64 *)u.dev, n, DownD8{h->ncode, h->geo}, usm.as<u32>(),
-                                                              err.as<u32>());
-    KCHK();
+    PFDCHK(pfd_import_cells<IMPORT_STRICT>(h, "subbasins_area", PFD_I64, u.dev, (u64)n, (u64)n, usm.as<u32>(), nullptr, err.dev()));
     pfd_seg_end(h, 1);
-    PFDCHK(sa_read_err(h, err.as<u32>()));  // (before anything is indexed with the list)
+    PFDCHK(sa_check_err(h, err));  // (before anything is indexed with the list)
   }
   PFDCHK(pfd_exact_seq_dev(h, oseq));  // (orders the cells: n_seq bounds the rounds)
   const u64 m = (u64)h->n_seq;
   PFDCHK(mark.alloc((size_t)n));
   i64 stats[4] = {0, 0, 0, 0};
   u64 marked = 0;
-  if (compare == PFD_COMPARE_F64) PFDCHK((sa_rounds<T, true>(h, upa, usm.as<u32>(), area_min, flags, mark.as<u8>(), err.as<u32>(), &marked, stats)));
-  else PFDCHK((sa_rounds<T, false>(h, upa, usm.as<u32>(), area_min, flags, mark.as<u8>(), err.as<u32>(), &marked, stats)));
+  if (compare == PFD_COMPARE_F64) PFDCHK((sa_rounds<T, true>(h, upa, usm.as<u32>(), area_min, flags, mark.as<u8>(), err, &marked, stats)));
+  else PFDCHK((sa_rounds<T, false>(h, upa, usm.as<u32>(), area_min, flags, mark.as<u8>(), err, &marked, stats)));
   if (stats_out)
     for (int q = 0; q < 4; ++q) stats_out[q] = stats[q];
   // the list: the sequence compacted by the marks
@@ -341,7 +307,7 @@ static int sa_t(pfd_raster *h, const void *uparea, double area_min, int compare,
   PFDCHK(idx.alloc(std::max<size_t>((size_t)k * sizeof(i64), 16)));
   PFDCHK(ids.alloc(std::max<size_t>((size_t)k * sizeof(u32), 16)));
   if (k) {
-    k_sa_widen<<<cdiv_u32(k, 256), 256, 0, h->stream>>>(sel.as<u32>(), k, idx.as<i64>(), ids.as<u32>());
+    k_number<u32><<<cdiv_u32(k, 256), 256, 0, h->stream>>>(sel.as<u32>(), k, false, idx.as<i64>(), ids.as<u32>());
     KCHK();
   }
   pfd_seg_end(h, 3);

@@ -6,6 +6,8 @@
 // float sum depends on that order.  Integer areas (unit="cell") are a histogram (atomics, exact in any order);
 // float areas are summed in the reference's order: cells of the exact idxs_seq order (order.hip) are stably
 // sorted by label, then ONE LANE per label adds its cells from first to last — bit-identical.
+// The segment walks further down stand on walks.h (opening checks, error word, list import, links); every rocprim call
+// takes its scratch through pfd_rocprim (lists.h).
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -93,12 +95,10 @@ static int ucat_sorted_cells(pfd_raster *h, const u32 *lab, const u8 *is_out, u3
   k_ucat_keys<<<cdiv_u32(m, 256), 256, 0, h->stream>>>(oseq.as<u32>(), m, lab, is_out, keys.as<u32>());
   int bits = 1;
   while ((1ull << bits) <= (u64)k) ++bits;
-  size_t tb = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys.as<u32>(), keys2.as<u32>(), oseq.as<u32>(), cells.as<u32>(), (size_t)m,
-                                   0u, (unsigned)bits, h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::radix_sort_pairs(tmp.p, tb, keys.as<u32>(), keys2.as<u32>(), oseq.as<u32>(), cells.as<u32>(), (size_t)m, 0u,
-                                   (unsigned)bits, h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::radix_sort_pairs(p, b, keys.as<u32>(), keys2.as<u32>(), oseq.as<u32>(), cells.as<u32>(), (size_t)m, 0u,
+                                     (unsigned)bits, h->stream);
+  }));
   k_seg_bounds<<<cdiv_u32(m, 256), 256, 0, h->stream>>>(keys2.as<u32>(), m, bounds.as<u32>(), bounds.as<u32>() + k);
   KCHK();
   if (seg_name) pfd_seg_end(h, 4);
@@ -176,10 +176,15 @@ static int ucat_float_wide(pfd_raster *h, const u32 *lab, const u8 *is_out, u32 
   PFDCHK(bounds.alloc(2 * (size_t)k * sizeof(u32)));
   int bits = 1;
   while ((1ull << bits) <= (u64)k) ++bits;
+  // one scratch, sized for the largest piece, serves the sort of every piece
+  auto sort_piece = [&](u64 m) {
+    return [&, m](void *p, size_t &b) {
+      return rocprim::radix_sort_pairs(p, b, keys.as<u32>(), keys2.as<u32>(), vals.as<T>(), vals2.as<T>(), (size_t)m, 0u,
+                                       (unsigned)bits, h->stream);
+    };
+  };
   size_t tb = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys.as<u32>(), keys2.as<u32>(), vals.as<T>(), vals2.as<T>(), (size_t)piece, 0u,
-                                   (unsigned)bits, h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
+  PFDCHK(pfd_rocprim_scratch(tmp, sort_piece(piece), &tb));
   pfd_seg_begin(h, "ucat_sums");
   i64 launches = 0;
   for (u64 p0 = 0; p0 < nseq; p0 += piece) {
@@ -187,8 +192,7 @@ static int ucat_float_wide(pfd_raster *h, const u32 *lab, const u8 *is_out, u32 
     k_ucat_pairs64<T><<<cdiv_u32(m, 256), 256, 0, h->stream>>>(q.as<u64>() + p0, m, lab, is_out, rows_dev, (u64)h->ncol, keys.as<u32>(),
                                                               vals.as<T>());
     size_t tb2 = tb;
-    HIPCHK(rocprim::radix_sort_pairs(tmp.p, tb2, keys.as<u32>(), keys2.as<u32>(), vals.as<T>(), vals2.as<T>(), (size_t)m, 0u,
-                                     (unsigned)bits, h->stream));
+    HIPCHK(sort_piece(m)(tmp.p, tb2));
     HIPCHK(hipMemsetAsync(bounds.p, 0, 2 * (size_t)k * sizeof(u32), h->stream));  // first = last = 0: empty segment
     k_seg_bounds<<<cdiv_u32(m, 256), 256, 0, h->stream>>>(keys2.as<u32>(), (u32)m, bounds.as<u32>(), bounds.as<u32>() + k);
     k_ucat_sum_wave<T><<<k, 64, 0, h->stream>>>(vals2.as<T>(), bounds.as<u32>(), bounds.as<u32>() + k, k, are_dev);
@@ -317,10 +321,6 @@ extern "C" int pfd_ucat_area(pfd_raster *h, const int64_t *idxs_out, int64_t k, 
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-template <class A, class B>
-struct Wider {
-  typedef typename std::conditional<std::is_same<A, double>::value || std::is_same<B, double>::value, double, float>::type type;
-};
 // np.maximum(0, x): 0 where 0 >= x, else x (a NaN stays)
 template <class T>
 __device__ __forceinline__ T vol_dh(T depth, T hand) {
@@ -393,16 +393,12 @@ static int vol_run(pfd_raster *h, const i64 *idx_dev, u32 k, u32 nd, const u32 *
   return PFD_OK;
 }
 
-static bool is_float_code(int c) { return c == PFD_F32 || c == PFD_F64; }
-
 }  // namespace
 
 extern "C" int pfd_ucat_volume(pfd_raster *h, const int64_t *idxs_out, int64_t k, int map_dtype, void *map_out, int hand_dtype,
                                const void *hand, int area_dtype, const void *area_rows, int depth_dtype, const void *depths,
                                int64_t ndepths, void *vol_out, int memspace) {
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_reject_general(h, "ucat_volume"));
-  PFDCHK(pfd_require_whole(h, "ucat_volume"));
+  PFDCHK(pfd_begin_whole(h, "ucat_volume"));
   if (!idxs_out || k < 0 || ndepths < 0 || !map_out || !hand || !area_rows || (ndepths && (!depths || !vol_out)) ||
       (u64)k * (u64)std::max<i64>(ndepths, 1) >= 0xFFFFFFFFull) {
     pfd_set_error("pfd_ucat_volume: bad arguments (NULL pointer, or %lld outlets x %lld depths)", (long long)k,
@@ -414,7 +410,6 @@ extern "C" int pfd_ucat_volume(pfd_raster *h, const int64_t *idxs_out, int64_t k
                   depth_dtype);
     return PFD_EUNSUPPORTED;
   }
-  pfd_seg_clear(h);
   DevBuf lab, is_out;
   PFDCHK(ucat_labels(h, "pfd_ucat_volume", idxs_out, k, lab, is_out));
   if (k && ndepths) {
@@ -460,50 +455,15 @@ extern "C" int pfd_ucat_volume(pfd_raster *h, const int64_t *idxs_out, int64_t k
 //           holds);
 //   FIXED   fixed_length_slope walks down while distnc > x0 (ends at a pit), then up the main stem while distnc < x1 (ends
 //           at a missing upstream cell).
-// Every walk ends after n steps with SG_CAP set: no kernel can spin on a cycle.  The walks are latency-bound gathers,
+// Every walk ends after n steps with WE_CAP set (walks.h): no kernel can spin on a cycle.  The outlet list is imported under
+// IMPORT_OUTLETS, idxs_us_main under IMPORT_ANY.  The walks are latency-bound gathers,
 // one dependent load per step; neighbouring lanes follow unrelated paths, so a wave runs as long as its longest segment.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-#define SG_MV 0xFFFFFFFFu
-enum { SG_CAP = 1, SG_INPUT = 2 };
-
-template <class D>
-struct NextDown {
-  D d;
-  __device__ __forceinline__ u32 operator()(u32 x) const { return (u32)d.down(x); }  // own index at a pit
-};
-struct NextUp {
-  const u32 *us;
-  __device__ __forceinline__ u32 operator()(u32 x) const { return us[x]; }  // SG_MV at a headwater
-};
-
-// the caller's lists in 32-bit lanes: a missing value becomes SG_MV, anything else outside [0, n) is an error
-__global__ void __launch_bounds__(256) k_sg_import_out(const i64 *__restrict__ in, u32 k, u64 n, u32 *__restrict__ out,
-                                                       u8 *__restrict__ flag, u32 *__restrict__ err) {
-  const u32 j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= k) return;
-  const i64 v = in[j];
-  u32 o = SG_MV;
-  if (v >= 0) {
-    if ((u64)v >= n) atomicOr(err, (u32)SG_INPUT);
-    else o = (u32)v, flag[o] = 1;
-  }
-  out[j] = o;
-}
-template <class I>
-__global__ void __launch_bounds__(256) k_sg_import_us(const I *__restrict__ in, u32 n, u32 *__restrict__ out,
-                                                      u32 *__restrict__ err) {
-  const u32 j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= n) return;
-  const I v = in[j];
-  u32 o = SG_MV;
-  if (v != (I)-1) {
-    if ((i64)v < 0 || (u64)v >= (u64)n) atomicOr(err, (u32)SG_INPUT);
-    else o = (u32)v;
-  }
-  out[j] = o;
-}
+// what the segment calls say about the shared findings of the error word
+const WalkErrText SG_TEXT = {"an index of idxs_out or idxs_us_main",
+                             "a walk did not end within n cells (the raster or idxs_us_main holds a cycle)"};
 
 // the cells of one segment, in walk order, handed to `visit`; false: the step cap was hit
 template <bool ONTO, class N, class F>
@@ -513,7 +473,7 @@ __device__ __forceinline__ bool sg_walk(const N &next, u32 idx0, const u8 *__res
   visit(idx0);
   for (;;) {
     const u32 idx1 = next(idx);
-    if (idx1 == SG_MV || idx1 == idx || (mask && !mask[idx1])) break;
+    if (idx1 == PFD_NOCELL || idx1 == idx || (mask && !mask[idx1])) break;
     if (!ONTO && flag[idx1]) break;
     idx = idx1;
     visit(idx);
@@ -537,9 +497,9 @@ __global__ void __launch_bounds__(256) k_sg_length(const N next, const u32 *__re
   if (i >= k) return;
   const u32 idx0 = out_idx[i];
   T v = (T)-9999;
-  if (idx0 != SG_MV) {
+  if (idx0 != PFD_NOCELL) {
     u32 lastc = idx0;
-    if (!sg_walk<true>(next, idx0, flag, mask, cap, [&](u32 x) { lastc = x; })) atomicOr(err, (u32)SG_CAP);
+    if (!sg_walk<true>(next, idx0, flag, mask, cap, [&](u32 x) { lastc = x; })) atomicOr(err, (u32)WE_CAP);
     v = sg_abs((T)(distnc[lastc] - distnc[idx0]));
   }
   res[i] = v;
@@ -560,7 +520,7 @@ __global__ void __launch_bounds__(256) k_sg_average(const N next, const u32 *__r
   if (i >= k) return;
   const u32 idx0 = out_idx[i];
   T r = nodata;
-  if (idx0 != SG_MV) {
+  if (idx0 != PFD_NOCELL) {
     P v = P(0);
     W w = W(0);
     const bool ok = sg_walk<false>(next, idx0, flag, mask, cap, [&](u32 x) {
@@ -570,7 +530,7 @@ __global__ void __launch_bounds__(256) k_sg_average(const N next, const u32 *__r
       v = v + (P)w0 * (P)v0;
       w = w + w0;
     });
-    if (!ok) atomicOr(err, (u32)SG_CAP);
+    if (!ok) atomicOr(err, (u32)WE_CAP);
     if (w != W(0)) r = (T)(v / (P)w);
   }
   res[i] = r;
@@ -585,9 +545,9 @@ __global__ void __launch_bounds__(256) k_sg_slope(const N next, const u32 *__res
   if (i >= k) return;
   const u32 idx0 = out_idx[i];
   E r = (E)-9999;
-  if (idx0 != SG_MV) {
+  if (idx0 != PFD_NOCELL) {
     u32 lastc = idx0;
-    if (!sg_walk<false>(next, idx0, flag, nullptr, cap, [&](u32 x) { lastc = x; })) atomicOr(err, (u32)SG_CAP);
+    if (!sg_walk<false>(next, idx0, flag, nullptr, cap, [&](u32 x) { lastc = x; })) atomicOr(err, (u32)WE_CAP);
     r = E(0);
     if (lastc != idx0) {
       const E dz = elevtn[idx0] - elevtn[lastc];
@@ -608,7 +568,7 @@ __global__ void __launch_bounds__(256) k_sg_fixed_slope(const D d, const u32 *__
   if (i >= k) return;
   u32 idx = out_idx[i];
   float r = -9999.f;
-  if (idx != SG_MV) {
+  if (idx != PFD_NOCELL) {
     const float x0 = distnc[idx] - half, x1 = distnc[idx] + half;
     u32 steps = 0;
     bool ok = true;
@@ -625,11 +585,11 @@ __global__ void __launch_bounds__(256) k_sg_fixed_slope(const D d, const u32 *__
     steps = 0;
     while (ok && distnc[idx] < x1) {
       const u32 up = us[idx];
-      if (up == SG_MV) break;
+      if (up == PFD_NOCELL) break;
       idx = up;
       if (++steps >= cap) ok = false;
     }
-    if (!ok) atomicOr(err, (u32)SG_CAP);
+    if (!ok) atomicOr(err, (u32)WE_CAP);
     r = 0.f;
     if (idx != first) r = (float)sg_abs((E)((elevtn[first] - elevtn[idx]) / (E)(distnc[first] - distnc[idx])));
   }
@@ -647,7 +607,7 @@ __global__ void __launch_bounds__(256) k_sg_collect(const N next, const u32 *__r
   if (i >= k) return;
   const u32 idx0 = out_idx[i];
   u32 c = 0;
-  if (idx0 != SG_MV) {
+  if (idx0 != PFD_NOCELL) {
     const u32 o = FILL ? off[i] : 0u;
     const bool ok = sg_walk<false>(next, idx0, flag, mask, cap, [&](u32 x) {
       const T v = data[x];
@@ -655,7 +615,7 @@ __global__ void __launch_bounds__(256) k_sg_collect(const N next, const u32 *__r
       if (FILL) vals[o + c] = v;
       ++c;
     });
-    if (!ok) atomicOr(err, (u32)SG_CAP);
+    if (!ok) atomicOr(err, (u32)WE_CAP);
   }
   if (!FILL) {
     cnt[i] = c;
@@ -669,7 +629,7 @@ __global__ void __launch_bounds__(256) k_sg_median(const u32 *__restrict__ out_i
   const u32 i = blockIdx.x * 256u + threadIdx.x;
   if (i >= k) return;
   T r = nodata;
-  if (out_idx[i] != SG_MV) {
+  if (out_idx[i] != PFD_NOCELL) {
     const u32 c = cnt[i], o = off[i];
     if (c == 0) r = (T)NAN;
     else if (c & 1u) r = sorted[o + c / 2];
@@ -680,29 +640,14 @@ __global__ void __launch_bounds__(256) k_sg_median(const u32 *__restrict__ out_i
 
 // what every segment call starts with: the outlet list in 32-bit lanes, the outlet flags, the main upstream cells
 struct SegCtx {
-  DevBuf out_idx, flag, us, err;
+  DevBuf out_idx, flag, us;
+  WalkErr err;
   InArg mask, oin, uin;
   u32 k = 0, cap = 0;
 };
-static int sg_read_err(pfd_raster *h, const u32 *dev, const char *what) {
-  u32 e = 0;
-  HIPCHK(hipMemcpyAsync(&e, dev, sizeof(e), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (e & SG_INPUT) {
-    pfd_set_error("%s: an index of idxs_out or idxs_us_main lies outside the raster", what);
-    return PFD_EINVAL;
-  }
-  if (e & SG_CAP) {
-    pfd_set_error("%s: a walk did not end within n cells (the raster or idxs_us_main holds a cycle)", what);
-    return PFD_EINVAL;
-  }
-  return PFD_OK;
-}
 static int sg_setup(pfd_raster *h, const char *what, const int64_t *idxs_out, int64_t k, bool need_us, int idx_dtype,
                     const void *idxs_us_main, const uint8_t *mask, const void *out, int memspace, SegCtx &c) {
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_reject_general(h, what));
-  PFDCHK(pfd_require_whole(h, what));
+  PFDCHK(pfd_begin_whole(h, what));
   if (k < 0 || k >= 0xFFFFFFFFll || (k && (!idxs_out || !out)) || (need_us && !idxs_us_main)) {
     pfd_set_error("%s: bad arguments (NULL pointer, or %lld outlets)", what, (long long)k);
     return PFD_EINVAL;
@@ -711,12 +656,10 @@ static int sg_setup(pfd_raster *h, const char *what, const int64_t *idxs_out, in
     pfd_set_error("%s: unsupported index dtype code %d", what, idx_dtype);
     return PFD_EUNSUPPORTED;
   }
-  pfd_seg_clear(h);
   c.k = (u32)k, c.cap = (u32)h->n;
   if (!k) return PFD_OK;
   const u32 n = (u32)h->n;
-  PFDCHK(c.err.alloc(sizeof(u32)));
-  HIPCHK(hipMemsetAsync(c.err.p, 0, sizeof(u32), h->stream));
+  PFDCHK(c.err.init(h));
   PFDCHK(c.out_idx.alloc((size_t)k * sizeof(u32)));
   PFDCHK(c.flag.alloc((size_t)n));
   HIPCHK(hipMemsetAsync(c.flag.p, 0, (size_t)n, h->stream));
@@ -724,20 +667,14 @@ static int sg_setup(pfd_raster *h, const char *what, const int64_t *idxs_out, in
   PFDCHK(c.mask.bind(mask, (size_t)n, memspace, h->stream));
   if (need_us) PFDCHK(c.uin.bind(idxs_us_main, (size_t)n * pfd_idx_bytes(idx_dtype), memspace, h->stream));
   pfd_seg_begin(h, "segment_import");
-  k_sg_import_out<<<cdiv_u32((u64)k, 256), 256, 0, h->stream>>>((const i64 *)c.oin.dev, c.k, (u64)n, c.out_idx.as<u32>(),
-                                                               c.flag.as<u8>(), c.err.as<u32>());
-  KCHK();
+  // (the rules of the two lists: walks.h.  The outlets raise their flags as they are imported)
+  PFDCHK(pfd_import_cells<IMPORT_OUTLETS>(h, what, PFD_I64, c.oin.dev, (u64)k, (u64)n, c.out_idx.as<u32>(), c.flag.as<u8>(), c.err.dev()));
   if (need_us) {
     PFDCHK(c.us.alloc((size_t)n * sizeof(u32)));
-    PFDCHK(pfd_dispatch_idx(idx_dtype, what, [&](auto itag) -> int {
-      typedef typename decltype(itag)::type I;
-      k_sg_import_us<I><<<cdiv_u32((u64)n, 256), 256, 0, h->stream>>>((const I *)c.uin.dev, n, c.us.as<u32>(), c.err.as<u32>());
-      KCHK();
-      return PFD_OK;
-    }));
+    PFDCHK(pfd_import_cells<IMPORT_ANY>(h, what, idx_dtype, c.uin.dev, (u64)n, (u64)n, c.us.as<u32>(), nullptr, c.err.dev()));
   }
   pfd_seg_end(h, need_us ? 2 : 1);
-  return sg_read_err(h, c.err.as<u32>(), what);  // (before anything is indexed with the lists)
+  return c.err.check(h, what, SG_TEXT);  // (before anything is indexed with the lists)
 }
 // f(next) with the walk's link: the decoded D8 codes downstream, the imported main upstream cells upstream
 template <class F>
@@ -766,12 +703,12 @@ static int sg_median_run(pfd_raster *h, int direction, SegCtx &c, const T *data,
   PFDCHK(sg_dispatch_dir(h, what, direction, c, [&](auto next) -> int {
     k_sg_collect<false><<<grid, 256, 0, h->stream>>>(next, c.out_idx.as<u32>(), k, c.flag.as<u8>(), (const u8 *)c.mask.dev, c.cap,
                                                      data, nodata, cnt.as<u32>(), (const u32 *)nullptr, (T *)nullptr,
-                                                     (unsigned long long *)total.p, c.err.as<u32>());
+                                                     (unsigned long long *)total.p, c.err.dev());
     KCHK();
     return PFD_OK;
   }));
   pfd_seg_end(h, 1);
-  PFDCHK(sg_read_err(h, c.err.as<u32>(), what));
+  PFDCHK(c.err.check(h, what, SG_TEXT));
   unsigned long long m = 0;
   HIPCHK(hipMemcpyAsync(&m, total.p, sizeof(m), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -780,10 +717,9 @@ static int sg_median_run(pfd_raster *h, int direction, SegCtx &c, const T *data,
     return PFD_EUNSUPPORTED;
   }
   pfd_seg_begin(h, "segment_median_sort");
-  size_t tb = 0;
-  HIPCHK(rocprim::exclusive_scan(nullptr, tb, cnt.as<u32>(), off.as<u32>(), 0u, (size_t)k, rocprim::plus<u32>(), h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::exclusive_scan(tmp.p, tb, cnt.as<u32>(), off.as<u32>(), 0u, (size_t)k, rocprim::plus<u32>(), h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *p, size_t &b) {
+    return rocprim::exclusive_scan(p, b, cnt.as<u32>(), off.as<u32>(), 0u, (size_t)k, rocprim::plus<u32>(), h->stream);
+  }));
   const u32 mm = (u32)m;
   HIPCHK(hipMemcpyAsync(off.as<u32>() + k, &mm, sizeof(u32), hipMemcpyHostToDevice, h->stream));
   i64 launches = 1;
@@ -793,18 +729,16 @@ static int sg_median_run(pfd_raster *h, int direction, SegCtx &c, const T *data,
     PFDCHK(sg_dispatch_dir(h, what, direction, c, [&](auto next) -> int {
       k_sg_collect<true><<<grid, 256, 0, h->stream>>>(next, c.out_idx.as<u32>(), k, c.flag.as<u8>(), (const u8 *)c.mask.dev, c.cap,
                                                       data, nodata, (u32 *)nullptr, off.as<u32>(), vals.as<T>(),
-                                                      (unsigned long long *)nullptr, c.err.as<u32>());
+                                                      (unsigned long long *)nullptr, c.err.dev());
       KCHK();
       return PFD_OK;
     }));
     // per segment, on rocprim's order-preserving radix keys of the float type (no NaN among the values)
-    size_t sb = 0;
-    HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, sb, vals.as<T>(), sorted.as<T>(), (unsigned int)m, (unsigned int)k,
-                                              off.as<u32>(), off.as<u32>() + 1, 0u, (unsigned int)(8 * sizeof(T)), h->stream));
     DevBuf stmp;
-    PFDCHK(stmp.alloc(std::max<size_t>(sb, 16)));
-    HIPCHK(rocprim::segmented_radix_sort_keys(stmp.p, sb, vals.as<T>(), sorted.as<T>(), (unsigned int)m, (unsigned int)k,
-                                              off.as<u32>(), off.as<u32>() + 1, 0u, (unsigned int)(8 * sizeof(T)), h->stream));
+    PFDCHK(pfd_rocprim(stmp, [&](void *p, size_t &b) {
+      return rocprim::segmented_radix_sort_keys(p, b, vals.as<T>(), sorted.as<T>(), (unsigned int)m, (unsigned int)k, off.as<u32>(),
+                                                off.as<u32>() + 1, 0u, (unsigned int)(8 * sizeof(T)), h->stream);
+    }));
     HIPCHK(hipStreamSynchronize(h->stream));  // (stmp is released here)
     launches += 3;
   }
@@ -842,15 +776,15 @@ extern "C" int pfd_segment_length(pfd_raster *h, const int64_t *idxs_out, int64_
     const u32 grid = cdiv_u32((u64)k, 256);
     if (dist_dtype == PFD_I32)
       k_sg_length<<<grid, 256, 0, h->stream>>>(next, c.out_idx.as<u32>(), c.k, c.flag.as<u8>(), (const u8 *)c.mask.dev, c.cap,
-                                               (const i32 *)dn.dev, (i32 *)o.dev, c.err.as<u32>());
+                                               (const i32 *)dn.dev, (i32 *)o.dev, c.err.dev());
     else
       k_sg_length<<<grid, 256, 0, h->stream>>>(next, c.out_idx.as<u32>(), c.k, c.flag.as<u8>(), (const u8 *)c.mask.dev, c.cap,
-                                               (const float *)dn.dev, (float *)o.dev, c.err.as<u32>());
+                                               (const float *)dn.dev, (float *)o.dev, c.err.dev());
     KCHK();
     return PFD_OK;
   }));
   pfd_seg_end(h, 1);
-  PFDCHK(sg_read_err(h, c.err.as<u32>(), what));
+  PFDCHK(c.err.check(h, what, SG_TEXT));
   return o.finish(h->stream);
 }
 
@@ -883,25 +817,25 @@ extern "C" int pfd_segment_slope(pfd_raster *h, const int64_t *idxs_out, int64_t
     const DownD8 d{h->ncode, h->geo};
     if (elev_dtype == PFD_F32)
       k_sg_fixed_slope<<<grid, 256, 0, h->stream>>>(d, c.us.as<u32>(), c.out_idx.as<u32>(), c.k, c.cap, (const float *)el.dev,
-                                                    (const float *)dn.dev, half, (float *)o.dev, c.err.as<u32>());
+                                                    (const float *)dn.dev, half, (float *)o.dev, c.err.dev());
     else
       k_sg_fixed_slope<<<grid, 256, 0, h->stream>>>(d, c.us.as<u32>(), c.out_idx.as<u32>(), c.k, c.cap, (const double *)el.dev,
-                                                    (const float *)dn.dev, half, (float *)o.dev, c.err.as<u32>());
+                                                    (const float *)dn.dev, half, (float *)o.dev, c.err.dev());
     KCHK();
   } else {
     PFDCHK(sg_dispatch_dir(h, what, direction, c, [&](auto next) -> int {
       if (elev_dtype == PFD_F32)
         k_sg_slope<<<grid, 256, 0, h->stream>>>(next, c.out_idx.as<u32>(), c.k, c.flag.as<u8>(), c.cap, (const float *)el.dev,
-                                                (const float *)dn.dev, (float *)o.dev, c.err.as<u32>());
+                                                (const float *)dn.dev, (float *)o.dev, c.err.dev());
       else
         k_sg_slope<<<grid, 256, 0, h->stream>>>(next, c.out_idx.as<u32>(), c.k, c.flag.as<u8>(), c.cap, (const double *)el.dev,
-                                                (const float *)dn.dev, (double *)o.dev, c.err.as<u32>());
+                                                (const float *)dn.dev, (double *)o.dev, c.err.dev());
       KCHK();
       return PFD_OK;
     }));
   }
   pfd_seg_end(h, 1);
-  PFDCHK(sg_read_err(h, c.err.as<u32>(), what));
+  PFDCHK(c.err.check(h, what, SG_TEXT));
   return o.finish(h->stream);
 }
 
@@ -936,7 +870,7 @@ extern "C" int pfd_segment_average(pfd_raster *h, const int64_t *idxs_out, int64
       typedef typename decltype(wt)::type W;
       k_sg_average<<<grid, 256, 0, h->stream>>>(next, c.out_idx.as<u32>(), c.k, c.flag.as<u8>(), (const u8 *)c.mask.dev, c.cap,
                                                 (const T *)da.dev, (const W *)we.dev, (T)nodata, nan, (T *)o.dev,
-                                                c.err.as<u32>());
+                                                c.err.dev());
     };
     if (dtype == PFD_F32 && weight_dtype == PFD_F32) launch(PfdTag<float>{}, PfdTag<float>{});
     else if (dtype == PFD_F32) launch(PfdTag<float>{}, PfdTag<double>{});
@@ -946,7 +880,7 @@ extern "C" int pfd_segment_average(pfd_raster *h, const int64_t *idxs_out, int64
     return PFD_OK;
   }));
   pfd_seg_end(h, 1);
-  PFDCHK(sg_read_err(h, c.err.as<u32>(), what));
+  PFDCHK(c.err.check(h, what, SG_TEXT));
   return o.finish(h->stream);
 }
 

@@ -14,18 +14,21 @@
 //   walk      one thread per coarse cell follows the fine downstream links from a start cell to a stop condition.  The
 //             walks are bounded by the network, not by cellsize; every walk is capped at n_fine steps and reports an error
 //             instead of spinning on a cycle (the reference's `while True` never returns there).
+// The error word of the walks and the import of upscale_error's lists are the shared ones of walks.h.
 // The effective area ri**0.5 + ci**0.5 <= R**0.5 depends on (ri, ci, cellsize) only: the host evaluates it in float64 and
 // uploads a byte mask — no square root is taken on the device.  The offset window of dmm_nextidx (R = cellsize / 2, `// R`
 // in float) is restated in doubled integers, exact for odd cellsize as well.
 #include <algorithm>
 
 #include "common.h"
+#include "walks.h"
 
 namespace {
 
-#define UP_MV 0xFFFFFFFFu
 enum { SEL_EDGE = 0, SEL_EFFAREA = 1 };
-enum { UE_CAP = 1, UE_NODS = 2, UE_INPUT = 4 };  // bits of the device error word
+enum { UE_NODS = WE_OWN };  // the calls' own bit of the error word (walks.h)
+const WalkErrText UP_TEXT = {"an index",
+                             "a walk along the fine flow directions did not end within n cells (the raster holds a cycle)"};
 
 // the fine raster, the coarse grid over it and the effective-area mask
 struct Up {
@@ -54,8 +57,8 @@ struct Up {
 // max of (uparea, -index): a NaN never wins, nothing wins against the initial (0, none) without uparea > 0
 template <class T>
 __device__ __forceinline__ void take(T &bu, u32 &bi, T u, u32 i) {
-  if (i == UP_MV) return;
-  if (u > bu || (u == bu && bi != UP_MV && i < bi)) bu = u, bi = i;
+  if (i == PFD_NOCELL) return;
+  if (u > bu || (u == bu && bi != PFD_NOCELL && i < bi)) bu = u, bi = i;
 }
 template <int SEL>
 __device__ __forceinline__ bool selected(const Up &f, u32 ri, u32 ci) {
@@ -74,7 +77,7 @@ __global__ void __launch_bounds__(256) k_rep_strip(const Up f, const T *__restri
   const bool active = t < W && col < f.g.ncol;
   const u32 ci = t % f.cs;  // (W is a multiple of cs)
   T bu = T(0);
-  u32 bi = UP_MV;
+  u32 bi = PFD_NOCELL;
   if (active) {
     const u64 r0 = (u64)R * f.cs, r1 = r0 + f.cs < f.g.nrow ? r0 + f.cs : f.g.nrow;
     for (u64 r = r0; r < r1; ++r) {
@@ -105,7 +108,7 @@ __global__ void __launch_bounds__(256) k_rep_cell(const Up f, const T *__restric
   const u64 r0 = (u64)R * f.cs, r1 = r0 + f.cs < f.g.nrow ? r0 + f.cs : f.g.nrow;
   const u64 c0 = (u64)C * f.cs, c1 = c0 + f.cs < f.g.ncol ? c0 + f.cs : f.g.ncol;
   T bu = T(0);
-  u32 bi = UP_MV;
+  u32 bi = PFD_NOCELL;
   for (u64 r = r0; r < r1; ++r)
     for (u64 c = c0 + t; c < c1; c += 256u) {
       const u32 i = (u32)(r * f.g.ncol + c);
@@ -131,15 +134,15 @@ __global__ void __launch_bounds__(256) k_outlet_walk(const Up f, const u32 *__re
   const u32 idx0 = blockIdx.x * 256u + threadIdx.x;
   if (idx0 >= f.n1) return;
   u32 sub = rep[idx0];
-  if (sub != UP_MV) {
+  if (sub != PFD_NOCELL) {
     u32 steps = 0;
     for (;;) {
       const u32 sub1 = f.down(sub);
       if (sub1 == sub || f.coarse(sub1) != idx0) break;
       sub = sub1;
       if (++steps >= f.g.n) {
-        atomicOr(err, (u32)UE_CAP);
-        sub = UP_MV;
+        atomicOr(err, (u32)WE_CAP);
+        sub = PFD_NOCELL;
         break;
       }
     }
@@ -153,8 +156,8 @@ __global__ void __launch_bounds__(256) k_next_dmm(const Up f, const u32 *__restr
   const u32 idx0 = blockIdx.x * 256u + threadIdx.x;
   if (idx0 >= f.n1) return;
   u32 sub = rep[idx0], idx = idx0;
-  if (sub == UP_MV) {
-    ds[idx0] = UP_MV;
+  if (sub == PFD_NOCELL) {
+    ds[idx0] = PFD_NOCELL;
     return;
   }
   u32 r, c;
@@ -174,8 +177,8 @@ __global__ void __launch_bounds__(256) k_next_dmm(const Up f, const u32 *__restr
     }
     sub = sub1, idx = idx1;
     if (++steps >= f.g.n) {
-      atomicOr(err, (u32)UE_CAP);
-      idx = UP_MV;
+      atomicOr(err, (u32)WE_CAP);
+      idx = PFD_NOCELL;
       break;
     }
   }
@@ -186,8 +189,8 @@ __global__ void __launch_bounds__(256) k_next_eam(const Up f, const u32 *__restr
                                                   u32 *__restrict__ err) {
   const u32 idx0 = blockIdx.x * 256u + threadIdx.x;
   if (idx0 >= f.n1) return;
-  u32 sub = rep[idx0], idx1 = UP_MV;
-  if (sub != UP_MV) {
+  u32 sub = rep[idx0], idx1 = PFD_NOCELL;
+  if (sub != PFD_NOCELL) {
     u32 steps = 0;
     for (;;) {
       const u32 sub1 = f.down(sub);
@@ -195,8 +198,8 @@ __global__ void __launch_bounds__(256) k_next_eam(const Up f, const u32 *__restr
       if (sub1 == sub || (idx1 != idx0 && f.effarea(sub1))) break;
       sub = sub1;
       if (++steps >= f.g.n) {
-        atomicOr(err, (u32)UE_CAP);
-        idx1 = UP_MV;
+        atomicOr(err, (u32)WE_CAP);
+        idx1 = PFD_NOCELL;
         break;
       }
     }
@@ -209,9 +212,9 @@ __global__ void __launch_bounds__(256) k_next_ihu(const Up f, const u32 *__restr
                                                   u32 *__restrict__ err) {
   const u32 idx0 = blockIdx.x * 256u + threadIdx.x;
   if (idx0 >= f.n1) return;
-  u32 sub = out[idx0], res = UP_MV;
-  if (sub != UP_MV) {
-    u32 sub_ds = UP_MV, steps = 0;
+  u32 sub = out[idx0], res = PFD_NOCELL;
+  if (sub != PFD_NOCELL) {
+    u32 sub_ds = PFD_NOCELL, steps = 0;
     bool capped = false;
     for (;;) {
       const u32 sub1 = f.down(sub);
@@ -221,43 +224,28 @@ __global__ void __launch_bounds__(256) k_next_ihu(const Up f, const u32 *__restr
         if (dr >= -1 && dr <= 1 && dc >= -1 && dc <= 1) sub_ds = sub1;
         break;
       }
-      if (sub_ds == UP_MV && f.effarea(sub1)) sub_ds = sub1;
+      if (sub_ds == PFD_NOCELL && f.effarea(sub1)) sub_ds = sub1;
       sub = sub1;
       if (++steps >= f.g.n) {
         capped = true;
         break;
       }
     }
-    if (capped) atomicOr(err, (u32)UE_CAP);
-    else if (sub_ds == UP_MV) atomicOr(err, (u32)UE_NODS);
+    if (capped) atomicOr(err, (u32)WE_CAP);
+    else if (sub_ds == PFD_NOCELL) atomicOr(err, (u32)UE_NODS);
     else res = f.coarse(sub_ds);
   }
   ds[idx0] = res;
 }
 
-// upscale_error: the caller's lists in 32-bit lanes (missing value -> UP_MV; anything else outside [0, limit) is an error)
-template <class I>
-__global__ void __launch_bounds__(256) k_import_idx(const I *__restrict__ in, u32 k, u64 limit, u32 *__restrict__ out,
-                                                    u32 *__restrict__ err) {
-  const u32 j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= k) return;
-  const I v = in[j];
-  u32 o = UP_MV;
-  if (v != (I)-1) {
-    const i64 w = (i64)v;
-    if (w < 0 || (u64)w >= limit) atomicOr(err, (u32)UE_INPUT);
-    else o = (u32)v;
-  }
-  out[j] = o;
-}
 template <class I>
 __global__ void __launch_bounds__(256) k_export_idx(const u32 *__restrict__ in, u32 k, I *__restrict__ out) {
   const u32 j = blockIdx.x * 256u + threadIdx.x;
-  if (j < k) out[j] = in[j] == UP_MV ? (I)-1 : (I)in[j];
+  if (j < k) out[j] = in[j] == PFD_NOCELL ? (I)-1 : (I)in[j];
 }
 __global__ void __launch_bounds__(256) k_flag_outlets(const u32 *__restrict__ out, u32 k, u8 *__restrict__ flag) {
   const u32 j = blockIdx.x * 256u + threadIdx.x;
-  if (j < k && out[j] != UP_MV) flag[out[j]] = 1;
+  if (j < k && out[j] != PFD_NOCELL) flag[out[j]] = 1;
 }
 __global__ void __launch_bounds__(256) k_error_walk(const u8 *__restrict__ ncode, const Geo g, const u32 *__restrict__ out,
                                                     const u32 *__restrict__ ds1, u32 k, const u8 *__restrict__ flag,
@@ -267,7 +255,7 @@ __global__ void __launch_bounds__(256) k_error_walk(const u8 *__restrict__ ncode
   u32 sub = out[idx0];
   const u32 idx_ds = ds1[idx0];
   u8 v = 255;
-  if (sub != UP_MV && idx_ds != UP_MV) {
+  if (sub != PFD_NOCELL && idx_ds != PFD_NOCELL) {
     u32 steps = 0;
     for (;;) {
       const u32 sub1 = d8_down(g, sub, ncode[sub]);
@@ -277,7 +265,7 @@ __global__ void __launch_bounds__(256) k_error_walk(const u8 *__restrict__ ncode
       }
       sub = sub1;
       if (++steps >= g.n) {
-        atomicOr(err, (u32)UE_CAP);
+        atomicOr(err, (u32)WE_CAP);
         break;
       }
     }
@@ -285,19 +273,11 @@ __global__ void __launch_bounds__(256) k_error_walk(const u8 *__restrict__ ncode
   res[idx0] = v;
 }
 
-static int read_err(pfd_raster *h, const u32 *dev, const char *what) {
-  u32 e = 0;
-  HIPCHK(hipMemcpyAsync(&e, dev, sizeof(e), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (e & UE_INPUT) {
-    pfd_set_error("%s: an index lies outside the raster", what);
-    return PFD_EINVAL;
-  }
-  if (e & UE_CAP) {
-    pfd_set_error("%s: a walk along the fine flow directions did not end within n cells (the raster holds a cycle)", what);
-    return PFD_EINVAL;
-  }
-  if (e & UE_NODS) {
+// the shared findings of the error word, then the calls' own
+static int up_check_err(pfd_raster *h, WalkErr &err, const char *what) {
+  u32 own = 0;
+  PFDCHK(err.check(h, what, UP_TEXT, &own));
+  if (own & UE_NODS) {
     pfd_set_error("%s: a coarse cell found neither an outlet within its 8 neighbours nor an effective area downstream "
                   "(the reference indexes with its missing value there)", what);
     return PFD_EINVAL;
@@ -306,14 +286,11 @@ static int read_err(pfd_raster *h, const u32 *dev, const char *what) {
 }
 
 static int check_fine(pfd_raster *h, const char *what, i64 cellsize) {
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_reject_general(h, what));
-  PFDCHK(pfd_require_whole(h, what));
+  PFDCHK(pfd_begin_whole(h, what));
   if (cellsize < 1 || cellsize > 0x7FFFFFFFll) {
     pfd_set_error("%s: cellsize %lld is not a positive 32-bit integer", what, (long long)cellsize);
     return PFD_EINVAL;
   }
-  pfd_seg_clear(h);
   return PFD_OK;
 }
 
@@ -395,23 +372,23 @@ static int upscale_impl(pfd_raster *h, const char *what, int method, i64 cellsiz
                    h->stream));
   const Up f = make_up(h, cellsize, (const u8 *)ea.dev);
   const size_t isz = pfd_idx_bytes(idx_dtype);
-  DevBuf out, ds, err;
+  DevBuf out, ds;
+  WalkErr err;
   PFDCHK(out.alloc((size_t)f.n1 * sizeof(u32)));
   if (idxs_ds_out) PFDCHK(ds.alloc((size_t)f.n1 * sizeof(u32)));
-  PFDCHK(err.alloc(sizeof(u32)));
-  HIPCHK(hipMemsetAsync(err.p, 0, sizeof(u32), h->stream));
+  PFDCHK(err.init(h));
   InArg upa;
   const size_t esz = uparea_dtype == PFD_I32 || uparea_dtype == PFD_F32 ? 4 : 8;
   PFDCHK(upa.bind(uparea, (size_t)h->n * esz, memspace, h->stream));
   switch (uparea_dtype) {
-    case PFD_I32: PFDCHK(upscale_run<i32>(h, method, f, (const i32 *)upa.dev, out.as<u32>(), ds.as<u32>(), err.as<u32>())); break;
-    case PFD_F32: PFDCHK(upscale_run<float>(h, method, f, (const float *)upa.dev, out.as<u32>(), ds.as<u32>(), err.as<u32>())); break;
-    case PFD_F64: PFDCHK(upscale_run<double>(h, method, f, (const double *)upa.dev, out.as<u32>(), ds.as<u32>(), err.as<u32>())); break;
+    case PFD_I32: PFDCHK(upscale_run<i32>(h, method, f, (const i32 *)upa.dev, out.as<u32>(), ds.as<u32>(), err.dev())); break;
+    case PFD_F32: PFDCHK(upscale_run<float>(h, method, f, (const float *)upa.dev, out.as<u32>(), ds.as<u32>(), err.dev())); break;
+    case PFD_F64: PFDCHK(upscale_run<double>(h, method, f, (const double *)upa.dev, out.as<u32>(), ds.as<u32>(), err.dev())); break;
     default:
       pfd_set_error("%s: uparea dtype code %d is not supported (int32, float32, float64)", what, uparea_dtype);
       return PFD_EUNSUPPORTED;
   }
-  PFDCHK(read_err(h, err.as<u32>(), what));
+  PFDCHK(up_check_err(h, err, what));
   return pfd_dispatch_idx(idx_dtype, what, [&](auto itag) -> int {
     typedef typename decltype(itag)::type I;
     OutArg o1, o2;
@@ -462,32 +439,27 @@ extern "C" int pfd_upscale_error(pfd_raster *h, int idx_dtype, const void *idxs_
   InArg a, b;
   PFDCHK(a.bind(idxs_out, (size_t)k * isz, memspace, h->stream));
   PFDCHK(b.bind(idxs_ds_coarse, (size_t)k * isz, memspace, h->stream));
-  DevBuf so, sd, flag, err;
+  DevBuf so, sd, flag;
+  WalkErr err;
   PFDCHK(so.alloc((size_t)k * sizeof(u32)));
   PFDCHK(sd.alloc((size_t)k * sizeof(u32)));
   PFDCHK(flag.alloc((size_t)h->n));
-  PFDCHK(err.alloc(sizeof(u32)));
-  HIPCHK(hipMemsetAsync(err.p, 0, sizeof(u32), h->stream));
+  PFDCHK(err.init(h));
   HIPCHK(hipMemsetAsync(flag.p, 0, (size_t)h->n, h->stream));
   const u32 grid = cdiv_u32((u64)k, 256);
-  PFDCHK(pfd_dispatch_idx(idx_dtype, "upscale_error", [&](auto itag) -> int {
-    typedef typename decltype(itag)::type I;
-    k_import_idx<I><<<grid, 256, 0, h->stream>>>((const I *)a.dev, (u32)k, (u64)h->n, so.as<u32>(), err.as<u32>());
-    KCHK();
-    k_import_idx<I><<<grid, 256, 0, h->stream>>>((const I *)b.dev, (u32)k, (u64)k, sd.as<u32>(), err.as<u32>());
-    KCHK();
-    return PFD_OK;
-  }));
-  PFDCHK(read_err(h, err.as<u32>(), "upscale_error"));  // (before anything is indexed with the lists)
+  // (fine cells, then coarse cells: IMPORT_ANY, there is no link to hold them against)
+  PFDCHK(pfd_import_cells<IMPORT_ANY>(h, "upscale_error", idx_dtype, a.dev, (u64)k, (u64)h->n, so.as<u32>(), nullptr, err.dev()));
+  PFDCHK(pfd_import_cells<IMPORT_ANY>(h, "upscale_error", idx_dtype, b.dev, (u64)k, (u64)k, sd.as<u32>(), nullptr, err.dev()));
+  PFDCHK(up_check_err(h, err, "upscale_error"));  // (before anything is indexed with the lists)
   OutArg o;
   PFDCHK(o.bind(out, (size_t)k, memspace));
   pfd_seg_begin(h, "upscale_error");
   k_flag_outlets<<<grid, 256, 0, h->stream>>>(so.as<u32>(), (u32)k, flag.as<u8>());
   KCHK();
   k_error_walk<<<grid, 256, 0, h->stream>>>(h->ncode, h->geo, so.as<u32>(), sd.as<u32>(), (u32)k, flag.as<u8>(), (u8 *)o.dev,
-                                            err.as<u32>());
+                                            err.dev());
   KCHK();
   pfd_seg_end(h, 2);
-  PFDCHK(read_err(h, err.as<u32>(), "upscale_error"));
+  PFDCHK(up_check_err(h, err, "upscale_error"));
   return o.finish(h->stream);
 }

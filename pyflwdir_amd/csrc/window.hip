@@ -12,10 +12,11 @@
 // list is imported), a lane needs no storage for it: it walks up u <= n steps, then makes ONE walk down, u steps back to the
 // centre and up to n steps beyond, which meets the cells in summation order (win_visit).
 //
+// The import of the caller's list, its error word, the links of a walk and the tail of pfd_path (count walk, scan, fill walk,
+// hand-over) are the shared ones of walks.h / lists.h; the windows import under IMPORT_DRAINS, the paths under IMPORT_ANY.
+//
 // The median keeps the window's values: a lane insertion-sorts their order-preserving integer keys, in LDS when the window
 // fits (2n + 1 <= WMAX), else in a strided global workspace that serves the raster in chunks of a fixed byte budget.
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <cmath>
 
@@ -24,8 +25,9 @@
 
 namespace {
 
-#define WN_MV 0xFFFFFFFFu
-enum { WN_CAP = 1, WN_INPUT = 2, WN_INVERSE = 4 };
+// what the window calls say about the shared findings of the error word
+const WalkErrText WIN_TEXT = {"an index of idxs_us_main",
+                              "a walk did not end within n_cells steps (the raster or idxs_us_main holds a cycle)"};
 
 // LDS budget of the small-window median ("Windows along the flow path"): slot * 256 + tid of 4-byte (float32)
 // or 8-byte (float64) keys; 31 * 256 * 4 = 31744 B and 15 * 256 * 8 = 30720 B per workgroup, i.e. about 124 B per lane,
@@ -44,11 +46,6 @@ struct WinCfg<double> {
 };
 constexpr u32 WIN_BLOCK = 256;
 constexpr size_t WIN_WS_BYTES = (size_t)256 << 20;  // byte budget of the large-window workspace
-
-template <class A, class B>
-struct Wider {
-  typedef typename std::conditional<std::is_same<A, double>::value || std::is_same<B, double>::value, double, float>::type type;
-};
 
 // order-preserving keys of the float types (total order: -0.0 < 0.0; no NaN is ever stored)
 __device__ __forceinline__ u32 key_of(float v) {
@@ -78,26 +75,6 @@ struct StrOrd {
   }
 };
 
-// the caller's main upstream cells in 32-bit lanes: the dtype's -1 becomes WN_MV, anything else outside [0, n) is an error;
-// `inverse`: every entry must drain into its cell (what lets the window be walked in one pass)
-template <class I>
-__global__ void __launch_bounds__(256) k_win_import_us(const I *__restrict__ in, u32 n, const DownD8 d, int inverse,
-                                                       u32 *__restrict__ out, u32 *__restrict__ err) {
-  const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
-  if (j >= n) return;
-  const I v = in[j];
-  u32 o = WN_MV;
-  if (v != (I)-1) {
-    if ((i64)v < 0 || (u64)v >= (u64)n) {
-      atomicOr(err, (u32)WN_INPUT);
-    } else {
-      o = (u32)v;
-      if (inverse && (u32)d.down(o) != (u32)j) atomicOr(err, (u32)WN_INVERSE);
-    }
-  }
-  out[j] = o;
-}
-
 // ---- downstream: out[x] = data[idxs_ds[x]] for a valid cell (a pit: itself), data[x] for a nodata cell -------------------
 template <class E>
 __global__ void __launch_bounds__(256) k_downstream(const DownD8 d, u32 n, const E *__restrict__ data, E *__restrict__ out) {
@@ -114,7 +91,7 @@ __device__ __forceinline__ void win_visit(const DownD8 &d, const u32 *__restrict
   u64 u = 0;
   while (u < n) {  // up the main stem
     const u32 y = us[x];
-    if (y == WN_MV) break;
+    if (y == PFD_NOCELL) break;
     x = y, ++u;
   }
   for (u64 i = 0; i < u; ++i) {  // back down to the centre
@@ -201,46 +178,25 @@ __global__ void __launch_bounds__(256) k_win_median(const DownD8 d, const u32 *_
 
 // what the two window calls start with
 struct WinCtx {
-  DevBuf us, err;
+  DevBuf us;
+  WalkErr err;
   InArg uin, sin;
   StrOrd so{nullptr, 0};
 };
-static bool is_float_code(int c) { return c == PFD_F32 || c == PFD_F64; }
-static int win_read_err(pfd_raster *h, const u32 *dev, const char *what) {
-  u32 e = 0;
-  HIPCHK(hipMemcpyAsync(&e, dev, sizeof(e), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (e & WN_INPUT) {
-    pfd_set_error("%s: an index of idxs_us_main lies outside the raster", what);
-    return PFD_EINVAL;
-  }
-  if (e & WN_INVERSE) {
-    pfd_set_error("%s: idxs_us_main holds a cell that does not drain into the cell it is listed for", what);
-    return PFD_EINVAL;
-  }
-  if (e & WN_CAP) {
-    pfd_set_error("%s: a walk did not end within n_cells steps (the raster or idxs_us_main holds a cycle)", what);
-    return PFD_EINVAL;
-  }
-  return PFD_OK;
-}
-static int win_import_us(pfd_raster *h, const char *what, int idx_dtype, const void *us_dev, int inverse, DevBuf &us,
-                         u32 *err_dev) {
-  const u32 n = (u32)h->n;
+// the caller's main upstream cells in 32-bit lanes under the call's import rule (walks.h), checked before anything is indexed
+// with them
+template <int CHECK>
+static int win_import_us(pfd_raster *h, const char *what, int idx_dtype, const void *us_dev, DevBuf &us, WalkErr &err) {
+  const u64 n = (u64)h->n;
+  pfd_seg_begin(h, "window_import");
   PFDCHK(us.alloc((size_t)n * sizeof(u32)));
-  return pfd_dispatch_idx(idx_dtype, what, [&](auto itag) -> int {
-    typedef typename decltype(itag)::type I;
-    k_win_import_us<I><<<cdiv_u32((u64)n, 256), 256, 0, h->stream>>>((const I *)us_dev, n, DownD8{h->ncode, h->geo}, inverse,
-                                                                    us.as<u32>(), err_dev);
-    KCHK();
-    return PFD_OK;
-  });
+  PFDCHK(pfd_import_cells<CHECK>(h, what, idx_dtype, us_dev, n, n, us.as<u32>(), nullptr, err.dev()));
+  pfd_seg_end(h, 1);
+  return err.check(h, what, WIN_TEXT);
 }
 static int win_setup(pfd_raster *h, const char *what, int64_t n, int idx_dtype, const void *idxs_us_main, int strord_dtype,
                      const void *strord, const void *data, const void *out, int memspace, WinCtx &c) {
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_reject_general(h, what));
-  PFDCHK(pfd_require_whole(h, what));
+  PFDCHK(pfd_begin_whole(h, what));
   if (n < 0 || n > ((int64_t)1 << 61) || !idxs_us_main || !data || !out) {
     pfd_set_error("%s: bad arguments (NULL pointer, or n = %lld)", what, (long long)n);
     return PFD_EINVAL;
@@ -257,16 +213,11 @@ static int win_setup(pfd_raster *h, const char *what, int64_t n, int idx_dtype, 
       return PFD_EUNSUPPORTED;
     }
   }
-  pfd_seg_clear(h);
-  PFDCHK(c.err.alloc(sizeof(u32)));
-  HIPCHK(hipMemsetAsync(c.err.p, 0, sizeof(u32), h->stream));
+  PFDCHK(c.err.init(h));
   PFDCHK(c.uin.bind(idxs_us_main, (size_t)h->n * pfd_idx_bytes(idx_dtype), memspace, h->stream));
   PFDCHK(c.sin.bind(strord, (size_t)h->n * ssz, memspace, h->stream));
   c.so = StrOrd{c.sin.dev, strord ? strord_dtype : 0};
-  pfd_seg_begin(h, "window_import");
-  PFDCHK(win_import_us(h, what, idx_dtype, c.uin.dev, 1, c.us, c.err.as<u32>()));
-  pfd_seg_end(h, 1);
-  return win_read_err(h, c.err.as<u32>(), what);  // (before anything is indexed with the list)
+  return win_import_us<IMPORT_DRAINS>(h, what, idx_dtype, c.uin.dev, c.us, c.err);
 }
 
 static size_t win_ws_budget() {
@@ -313,14 +264,6 @@ static int win_median_run(pfd_raster *h, WinCtx &c, int64_t n, const T *data, T 
 }
 
 // ---- path: core._trace per start cell, as a count walk, a scan and a fill walk -----------------------------------------
-struct PathDown {
-  DownD8 d;
-  __device__ __forceinline__ u32 operator()(u32 x) const { return (u32)d.down(x); }  // own index at a pit / nodata cell
-};
-struct PathUp {
-  const u32 *us;
-  __device__ __forceinline__ u32 operator()(u32 x) const { return us[x]; }  // WN_MV at a headwater
-};
 // FILL = false: the length and the distance of path i; FILL = true: its cells at off[i]
 template <bool FILL, class N, class O>
 __global__ void __launch_bounds__(256) k_path(const N next, const Geo g, const i64 *__restrict__ start, u32 k,
@@ -337,7 +280,7 @@ __global__ void __launch_bounds__(256) k_path(const N next, const Geo g, const i
   for (u32 nstep = 0;; ++nstep) {
     if (mask && mask[x]) break;  // (the first masked cell is part of the path)
     const u32 y = next(x);
-    if (y == WN_MV || y == x) break;
+    if (y == PFD_NOCELL || y == x) break;
     double step = 1.0;
     if (steps) {
       const u32 r0 = geo_row(g, x), r1 = geo_row(g, y);
@@ -347,7 +290,7 @@ __global__ void __launch_bounds__(256) k_path(const N next, const Geo g, const i
     }
     if (has_max && dsum + step > max_length) break;
     if (nstep >= cap) {  // (n_cells steps: a cycle)
-      atomicOr(err, (u32)WN_CAP);
+      atomicOr(err, (u32)WE_CAP);
       break;
     }
     dsum += step;
@@ -370,14 +313,11 @@ extern "C" int pfd_debug_window_wmax(int dtype, int *wmax) {
 }
 
 extern "C" int pfd_downstream(pfd_raster *h, int elem_bytes, const void *data, void *out, int memspace) {
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_reject_general(h, "downstream"));
-  PFDCHK(pfd_require_whole(h, "downstream"));
+  PFDCHK(pfd_begin_whole(h, "downstream"));
   if (!data || !out || (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8)) {
     pfd_set_error("pfd_downstream: bad arguments (NULL pointer, or elements of %d bytes: 1, 2, 4 or 8)", elem_bytes);
     return data && out ? PFD_EUNSUPPORTED : PFD_EINVAL;
   }
-  pfd_seg_clear(h);
   const u32 n = (u32)h->n, grid = cdiv_u32((u64)n, 256);
   InArg da;
   PFDCHK(da.bind(data, (size_t)h->n * elem_bytes, memspace, h->stream));
@@ -456,9 +396,7 @@ extern "C" int pfd_path(pfd_raster *h, const int64_t *idxs, int64_t k, int direc
                         void *idxs_out, int64_t cap_idxs, int64_t *offsets_out, double *dist_out, int64_t *n_out,
                         int memspace) {
   const char *what = "path";
-  PFDCHK(pfd_check_handle(h));
-  PFDCHK(pfd_reject_general(h, what));
-  PFDCHK(pfd_require_whole(h, what));
+  PFDCHK(pfd_begin_whole(h, what));
   if (k < 0 || k >= 0xFFFFFFFFll || (k && !idxs) || !n_out || cap_idxs < 0 || (cap_idxs > 0 && (!idxs_out || !offsets_out || !dist_out)) ||
       (direction != PFD_UP && direction != PFD_DOWN) || (direction == PFD_UP && !idxs_us_main)) {
     pfd_set_error("path: bad arguments (NULL pointer, %lld start cells, cap_idxs=%lld, direction code %d)", (long long)k,
@@ -474,83 +412,43 @@ extern "C" int pfd_path(pfd_raster *h, const int64_t *idxs, int64_t k, int direc
       pfd_set_error("path: start index %lld outside the raster", (long long)idxs[i]);
       return PFD_EINVAL;
     }
-  pfd_seg_clear(h);
   *n_out = 0;
-  if (!k) {
-    if (offsets_out) {
-      if (memspace == PFD_DEVICE) HIPCHK(hipMemsetAsync(offsets_out, 0, sizeof(i64), h->stream));
-      else offsets_out[0] = 0;
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return PFD_OK;
-  }
+  if (!k) return give_empty(h, offsets_out, memspace);
   const u32 ku = (u32)k, grid = cdiv_u32((u64)k, 256), cap = (u32)h->n;
-  DevBuf err, us, off, dist, tmp;
+  WalkErr err;
+  DevBuf us, dist;
   InArg di, dm, du, ds;
-  PFDCHK(err.alloc(sizeof(u32)));
-  HIPCHK(hipMemsetAsync(err.p, 0, sizeof(u32), h->stream));
+  PFDCHK(err.init(h));
   PFDCHK(di.bind(idxs, (size_t)k * sizeof(i64), PFD_HOST, h->stream));
   PFDCHK(dm.bind(mask, (size_t)h->n, memspace, h->stream));
   PFDCHK(ds.bind(step_lengths, (size_t)(2 * h->nrow - 1) * 3 * sizeof(double), PFD_HOST, h->stream));
   if (direction == PFD_UP) {
     PFDCHK(du.bind(idxs_us_main, (size_t)h->n * pfd_idx_bytes(idx_dtype), memspace, h->stream));
-    pfd_seg_begin(h, "window_import");
-    PFDCHK(win_import_us(h, what, idx_dtype, du.dev, 0, us, err.as<u32>()));
-    pfd_seg_end(h, 1);
-    PFDCHK(win_read_err(h, err.as<u32>(), what));
+    PFDCHK(win_import_us<IMPORT_ANY>(h, what, idx_dtype, du.dev, us, err));
   }
-  PFDCHK(off.alloc(((size_t)k + 1) * sizeof(i64)));
   PFDCHK(dist.alloc((size_t)k * sizeof(double)));
-  HIPCHK(hipMemsetAsync(off.as<i64>() + k, 0, sizeof(i64), h->stream));
   const DownD8 d{h->ncode, h->geo};
-  auto walk = [&](auto fill, auto itag, void *dst) -> int {
+  // the count walk (FILL = false: lengths into `lens`, distances into `dist`) and the fill walk (cells at dst + off[i])
+  auto walk = [&](auto fill, auto itag, i64 *lens, const i64 *off, void *dst) -> int {
     typedef typename decltype(itag)::type I;
     constexpr bool FILL = decltype(fill)::value;
-    if (direction == PFD_DOWN)
-      k_path<FILL, PathDown, I><<<grid, 256, 0, h->stream>>>(PathDown{d}, h->geo, (const i64 *)di.dev, ku, (const u8 *)dm.dev,
-                                                            (const double *)ds.dev, max_length, has_max_length, cap,
-                                                            off.as<i64>(), dist.as<double>(), off.as<i64>(), (I *)dst,
-                                                            err.as<u32>());
-    else
-      k_path<FILL, PathUp, I><<<grid, 256, 0, h->stream>>>(PathUp{us.as<u32>()}, h->geo, (const i64 *)di.dev, ku, (const u8 *)dm.dev,
-                                                          (const double *)ds.dev, max_length, has_max_length, cap,
-                                                          off.as<i64>(), dist.as<double>(), off.as<i64>(), (I *)dst,
-                                                          err.as<u32>());
+    auto launch = [&](auto next) {
+      k_path<FILL, decltype(next), I><<<grid, 256, 0, h->stream>>>(next, h->geo, (const i64 *)di.dev, ku, (const u8 *)dm.dev,
+                                                                 (const double *)ds.dev, max_length, has_max_length, cap, lens,
+                                                                 dist.as<double>(), off, (I *)dst, err.dev());
+    };
+    if (direction == PFD_DOWN) launch(NextDown<DownD8>{d});
+    else launch(NextUp{us.as<u32>()});
     KCHK();
     return PFD_OK;
   };
-  pfd_seg_begin(h, "path_count");
-  PFDCHK(walk(std::false_type{}, PfdTag<i64>{}, nullptr));
-  pfd_seg_end(h, 1);
-  PFDCHK(win_read_err(h, err.as<u32>(), what));
-  pfd_seg_begin(h, "path_offsets");
-  size_t tb = 0;
-  HIPCHK(rocprim::exclusive_scan(nullptr, tb, off.as<i64>(), off.as<i64>(), (i64)0, (size_t)k + 1, rocprim::plus<i64>(), h->stream));
-  PFDCHK(tmp.alloc(std::max<size_t>(tb, 16)));
-  HIPCHK(rocprim::exclusive_scan(tmp.p, tb, off.as<i64>(), off.as<i64>(), (i64)0, (size_t)k + 1, rocprim::plus<i64>(), h->stream));
-  pfd_seg_end(h, 1);
-  i64 total = 0;
-  HIPCHK(hipMemcpyAsync(&total, off.as<i64>() + k, sizeof(total), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  *n_out = total;
-  if (total > cap_idxs) return PFD_OK;
-  PFDCHK(pfd_dispatch_idx(idx_dtype, what, [&](auto itag) -> int {
-    typedef typename decltype(itag)::type I;
-    DevBuf stage;
-    I *dst = (I *)idxs_out;
-    if (memspace != PFD_DEVICE) {
-      PFDCHK(stage.alloc((size_t)total * sizeof(I)));
-      dst = stage.as<I>();
-    }
-    pfd_seg_begin(h, "path_fill");
-    PFDCHK(walk(std::true_type{}, itag, dst));
-    pfd_seg_end(h, 1);
-    if (memspace != PFD_DEVICE) PFDCHK(give_list(h, stage.p, (size_t)total * sizeof(I), idxs_out, memspace));
-    else HIPCHK(hipStreamSynchronize(h->stream));
-    return PFD_OK;
-  }));
-  PFDCHK(give_list(h, off.p, ((size_t)k + 1) * sizeof(i64), offsets_out, memspace));
-  PFDCHK(give_list(h, dist.p, (size_t)k * sizeof(double), dist_out, memspace));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  const RaggedSegs segs = {"path_count", "path_offsets", "path_fill", what};
+  const RaggedOut ro = {idx_dtype, idxs_out, cap_idxs, offsets_out, INT64_MAX, memspace};
+  bool given = false;
+  PFDCHK(pfd_ragged_tail(
+      h, segs, (u64)k, ro, [&](i64 *lens) { return walk(std::false_type{}, PfdTag<i64>{}, lens, nullptr, nullptr); },
+      [&] { return err.check(h, what, WIN_TEXT); },
+      [&](auto itag, const i64 *off, auto *dst) { return walk(std::true_type{}, itag, nullptr, off, dst); }, n_out, &given));
+  if (given) PFDCHK(give_list(h, dist.p, (size_t)k * sizeof(double), dist_out, memspace));
   return PFD_OK;
 }
