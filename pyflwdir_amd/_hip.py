@@ -38,29 +38,125 @@ STRORD_CODE = {np.dtype(np.uint8): PFD_U8, np.dtype(np.int32): PFD_I32, np.dtype
 _ERRORS = {-1: ValueError, -2: RuntimeError, -3: RuntimeError, -4: MemoryError, -5: ValueError,
            -6: ValueError, -7: NotImplementedError, -8: RuntimeError}
 
-# every symbol include/pfd.h declares (tests check that the library exports all of them)
-SYMBOLS = [
-    "pfd_abi_version", "pfd_last_error", "pfd_device_count", "pfd_malloc", "pfd_free", "pfd_memcpy_h2d",
-    "pfd_memcpy_d2h", "pfd_device_synchronize", "pfd_trim", "pfd_raster_create", "pfd_raster_create_block",
-    "pfd_raster_create_deferred", "pfd_raster_validate",
-    "pfd_raster_destroy", "pfd_raster_info", "pfd_upstream_area_cell_blocks", "pfd_comm_unique_id", "pfd_comm_create",
-    "pfd_comm_destroy", "pfd_comm_info", "pfd_upstream_area_cell_dist", "pfd_upstream_area_cell_begin", "pfd_upstream_area_cell_finish",
-    "pfd_add_pits", "pfd_idxs_ds", "pfd_idxs_pit", "pfd_upstream_count", "pfd_order_cells", "pfd_idxs_seq",
-    "pfd_rank", "pfd_upstream_area_cell", "pfd_upstream_area_cell_levels", "pfd_accuflux", "pfd_strahler",
-    "pfd_accuflux_rows", "pfd_basins", "pfd_hand", "pfd_main_upstream", "pfd_stream_order_classic", "pfd_stream_distance", "pfd_set_profiling", "pfd_last_timing", "pfd_synth_d8", "pfd_synth_elev_f32",
-    "pfd_synth_weights_f32", "pfd_graph_stats", "pfd_verify_upstream_area_cell", "pfd_verify_basins", "pfd_verify_hand", "pfd_hand_block", "pfd_accuflux_block", "pfd_strahler_block", "pfd_stream_distance_block", "pfd_checksum_i32", "pfd_basins_begin", "pfd_basins_finish", "pfd_fill_depressions", "pfd_ucat_area", "pfd_floodplains", "pfd_snap_downstream", "pfd_snap", "pfd_raster_create_general", "pfd_set_idxs_seq", "pfd_upstream_sum",
-    "pfd_comm_exchange_rows", "pfd_comm_allgather_host", "pfd_set_block_io", "pfd_synth_mosaic", "pfd_calib_traffic", "pfd_set_block_update",
-    "pfd_reserve", "pfd_alloc_stats", "pfd_mem_info", "pfd_transfer_stats", "pfd_count_nonfinite", "pfd_floodplains_block", "pfd_trib_info_block",
-    "pfd_stream_order_classic_block", "pfd_upstream_area_rows_fixed", "pfd_floodplains_block_flags",
-    "pfd_fillnodata", "pfd_fillnodata_block",
-    "pfd_subbasins_streamorder", "pfd_outflow_idxs", "pfd_basin_outlets",
-    "pfd_streams",
-    "pfd_interbasin_mask", "pfd_inflow_idxs", "pfd_basin_bounds", "pfd_subbasins_pfafstetter",
-    "pfd_subbasins_area",
-    "pfd_upscale", "pfd_upscale_outlets", "pfd_upscale_error",
-    "pfd_ucat_volume", "pfd_segment_length", "pfd_segment_slope", "pfd_segment_average", "pfd_segment_median",
-    "pfd_downstream", "pfd_moving_average", "pfd_moving_median", "pfd_path", "pfd_debug_window_wmax",
-]
+def _signatures():
+    """(return type, [argument types]) of every function include/pfd.h declares, one row per prototype and in the
+    header's order (tests/test_cabi.py holds every row to the header).  Untyped (`void *`), uint8 / int8 / int32 /
+    uint32 / float and handle pointers are ``p``; the typed pointers below are the ones the wrappers pass ctypes
+    arrays or ``byref`` values for."""
+    i, i32, i64, u64, sz, f64 = C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_double
+    p, s, pp = C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)
+    pi, pi64, pf64 = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    synth = [i, u64, i64, i64, i64, i64, i32, i64, i64, p]
+    return {
+        "pfd_abi_version": (i, []),
+        "pfd_last_error": (s, []),
+        "pfd_device_count": (i, [pi]),
+        "pfd_malloc": (i, [i, sz, pp]),
+        "pfd_free": (i, [i, p]),
+        "pfd_memcpy_h2d": (i, [i, p, p, sz]),
+        "pfd_memcpy_d2h": (i, [i, p, p, sz]),
+        "pfd_device_synchronize": (i, [i]),
+        "pfd_trim": (i, [i]),
+        "pfd_reserve": (i, [i, sz]),
+        "pfd_alloc_stats": (i, [pi64]),
+        "pfd_mem_info": (i, [i, pi64]),
+        "pfd_transfer_stats": (i, [pf64, i]),
+        "pfd_raster_create": (i, [p, i64, i64, i, i, pp]),
+        "pfd_raster_destroy": (i, [p]),
+        "pfd_raster_create_general": (i, [p, i, i64, i64, i, i, pp]),
+        "pfd_raster_create_block": (i, [p, i64, i64, i, i, i, i, pp]),
+        "pfd_raster_create_deferred": (i, [p, i64, i64, i, i, i, i, pp]),
+        "pfd_raster_validate": (i, [p]),
+        "pfd_raster_info": (i, [p, pi64]),
+        "pfd_add_pits": (i, [p, p, i64]),
+        "pfd_idxs_ds": (i, [p, i, p, i]),
+        "pfd_idxs_pit": (i, [p, i, p, i]),
+        "pfd_upstream_count": (i, [p, p, p, i]),
+        "pfd_order_cells": (i, [p]),
+        "pfd_idxs_seq": (i, [p, i, p, i]),
+        "pfd_set_idxs_seq": (i, [p, i, p, i64]),
+        "pfd_rank": (i, [p, p, i]),
+        "pfd_upstream_area_cell": (i, [p, p, i]),
+        "pfd_upstream_area_cell_levels": (i, [p, p, i]),
+        "pfd_accuflux": (i, [p, i, p, i64, f64, i, i, i, p, i]),
+        "pfd_accuflux_rows": (i, [p, i, p, i64, f64, i, i, i, p, i]),
+        "pfd_fillnodata": (i, [p, i, p, i64, f64, i, i, i, p, i]),
+        "pfd_upstream_area_rows_fixed": (i, [p, p, p, i, pi, pf64]),
+        "pfd_strahler": (i, [p, p, p, i]),
+        "pfd_basins": (i, [p, p, p, i64, i, p, i]),
+        "pfd_hand": (i, [p, p, i, p, p, i]),
+        "pfd_main_upstream": (i, [p, i, p, f64, i, p, i]),
+        "pfd_upstream_sum": (i, [p, i, p, i64, f64, i, p, i]),
+        "pfd_stream_order_classic": (i, [p, i, p, p, p, i]),
+        "pfd_stream_distance": (i, [p, p, i, p, p, i]),
+        "pfd_upstream_area_cell_blocks": (i, [pp, i, pp, i]),
+        "pfd_comm_unique_id": (i, [p, sz]),
+        "pfd_comm_create": (i, [p, sz, i, i, i, pp]),
+        "pfd_comm_destroy": (i, [p]),
+        "pfd_comm_info": (i, [p, pi, pi, pi]),
+        "pfd_upstream_area_cell_dist": (i, [p, p, p, i]),
+        "pfd_comm_exchange_rows": (i, [p, p, p, i, p, p]),
+        "pfd_comm_allgather_host": (i, [p, p, p, sz, p]),
+        "pfd_set_block_io": (i, [p, i]),
+        "pfd_upstream_area_cell_begin": (i, [p, p, i, p]),
+        "pfd_upstream_area_cell_finish": (i, [p, p, i, i, pi]),
+        "pfd_hand_block": (i, [p, p, i, p, p, i, p, i, p, pi64]),
+        "pfd_set_block_update": (i, [p, i]),
+        "pfd_accuflux_block": (i, [p, i, p, i, i64, f64, i, i, p, i, p, i, p, pi64]),
+        "pfd_strahler_block": (i, [p, p, p, i, p, i, p, pi64]),
+        "pfd_fillnodata_block": (i, [p, i, p, i64, f64, i, i, i, p, i, p, i, p, pi64]),
+        "pfd_stream_distance_block": (i, [p, p, i, p, p, i, p, i, p, pi64]),
+        "pfd_floodplains_block": (i, [p, i, p, p, p, p, i, p, i, p, pi64]),
+        "pfd_floodplains_block_flags": (i, [p, p, p, i]),
+        "pfd_trib_info_block": (i, [p, i, p, f64, p, p, i]),
+        "pfd_stream_order_classic_block": (i, [p, p, p, p, i, p, i, p, pi64]),
+        "pfd_basins_begin": (i, [p, p, p, i64, i, p, i, p]),
+        "pfd_basins_finish": (i, [p, p, i, i, pi]),
+        "pfd_fill_depressions": (i, [i, p, i64, i64, f64, f64, i, i, f64, p, i64, i, p, p]),
+        "pfd_ucat_area": (i, [p, p, i64, i, p, i, i, p, p]),
+        "pfd_ucat_volume": (i, [p, p, i64, i, p, i, p, i, p, i, p, i64, p, i]),
+        "pfd_segment_length": (i, [p, p, i64, i, i, p, p, i, p, p, i]),
+        "pfd_segment_slope": (i, [p, p, i64, i, i, p, i, p, p, f64, p, i]),
+        "pfd_segment_average": (i, [p, p, i64, i, i, p, p, i, p, i, p, f64, p, i]),
+        "pfd_segment_median": (i, [p, p, i64, i, i, p, p, i, p, f64, p, i]),
+        "pfd_subbasins_streamorder": (i, [p, i, p, i64, i, p, i64, pi64, p, i]),
+        "pfd_outflow_idxs": (i, [p, p, i, p, i64, pi64, i]),
+        "pfd_basin_outlets": (i, [p, i, p, i, p, p, i64, pi64, i]),
+        "pfd_interbasin_mask": (i, [p, p, p, p, i]),
+        "pfd_inflow_idxs": (i, [p, p, i, p, i64, pi64, i]),
+        "pfd_basin_bounds": (i, [p, i, p, p, p, i64, pi64, i]),
+        "pfd_subbasins_pfafstetter": (i, [p, i, p, f64, i, p, p, i64, i, p, i64, pi64, p, i]),
+        "pfd_subbasins_area": (i, [p, i, p, f64, i, p, i, p, i64, pi64, p, p, i, i]),
+        "pfd_streams": (i, [p, p, i, p, i64, p, p, i64, pi64, i]),
+        "pfd_upscale": (i, [p, i, i64, i, p, p, i, p, p, i]),
+        "pfd_upscale_outlets": (i, [p, i, i64, i, p, p, i, p, i]),
+        "pfd_upscale_error": (i, [p, i, p, p, i64, p, i]),
+        "pfd_downstream": (i, [p, i, p, p, i]),
+        "pfd_moving_average": (i, [p, i64, i, p, i, p, i, p, i, p, f64, p, i]),
+        "pfd_moving_median": (i, [p, i64, i, p, i, p, i, p, f64, p, i]),
+        "pfd_path": (i, [p, p, i64, i, i, p, p, p, i, f64, p, i64, p, p, pi64, i]),
+        "pfd_debug_window_wmax": (i, [i, pi]),
+        "pfd_floodplains": (i, [p, i, p, p, p, p, i]),
+        "pfd_snap_downstream": (i, [p, p, i64, p, i, i64, p, p]),
+        "pfd_snap": (i, [p, p, i64, p, p, p, i, f64, p, p]),
+        "pfd_set_profiling": (i, [p, i]),
+        "pfd_last_timing": (i, [p, i, p, p, s, sz, pi]),
+        "pfd_graph_stats": (i, [p, pi64]),
+        "pfd_verify_upstream_area_cell": (i, [p, p, i, pi64]),
+        "pfd_verify_basins": (i, [p, p, p, i64, p, i, pi64]),
+        "pfd_verify_hand": (i, [p, p, i, p, p, i, pi64]),
+        "pfd_checksum_i32": (i, [i, p, i64, pi64]),
+        "pfd_count_nonfinite": (i, [i, i, p, i64, pi64]),
+        "pfd_synth_d8": (i, synth),
+        "pfd_synth_elev_f32": (i, synth),
+        "pfd_synth_mosaic": (i, [i, p, i64, i64, i64, i64, p]),
+        "pfd_calib_traffic": (i, [i, p, sz, i, i]),
+        "pfd_synth_weights_f32": (i, [i, u64, i64, i64, p]),
+    }
+
+
+SIGNATURES = _signatures()
+SYMBOLS = list(SIGNATURES)  # every symbol include/pfd.h declares
 
 _lib = None
 
@@ -78,138 +174,9 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build the HIP extension first (python -m pyflwdir_amd.build, "
                 "needs hipcc/ROCm).  pyflwdir_amd has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        L.pfd_last_error.restype = C.c_char_p
-        for name in SYMBOLS:
-            if name != "pfd_last_error":
-                getattr(L, name).restype = C.c_int
-        L.pfd_raster_create.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.pfd_raster_create_block.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              C.POINTER(C.c_void_p)]
-        L.pfd_raster_create_deferred.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              C.POINTER(C.c_void_p)]
-        L.pfd_upstream_area_cell_blocks.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int]
-        L.pfd_comm_unique_id.argtypes = [C.c_void_p, C.c_size_t]
-        L.pfd_comm_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.pfd_comm_destroy.argtypes = [C.c_void_p]
-        L.pfd_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.pfd_upstream_area_cell_dist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_upstream_area_cell_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.pfd_upstream_area_cell_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
-        L.pfd_raster_destroy.argtypes = [C.c_void_p]
-        L.pfd_raster_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        L.pfd_add_pits.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-        L.pfd_idxs_ds.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.pfd_idxs_pit.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.pfd_idxs_seq.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.pfd_upstream_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_order_cells.argtypes = [C.c_void_p]
-        L.pfd_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_upstream_area_cell.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_upstream_area_cell_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_accuflux.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int,
-                                   C.c_int, C.c_void_p, C.c_int]
-        L.pfd_accuflux_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int,
-                                   C.c_int, C.c_void_p, C.c_int]
-        L.pfd_upstream_area_rows_fixed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
-                                                   C.POINTER(C.c_double)]
-        L.pfd_floodplains_block_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_strahler.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_basins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int]
-        L.pfd_hand.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_accuflux_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
-        L.pfd_fillnodata.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p, C.c_int]
-        L.pfd_fillnodata_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
-        L.pfd_subbasins_streamorder.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                                C.POINTER(C.c_int64), C.c_void_p, C.c_int]
-        L.pfd_outflow_idxs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]
-        L.pfd_basin_outlets.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
-                                        C.POINTER(C.c_int64), C.c_int]
-        L.pfd_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                  C.POINTER(C.c_int64), C.c_int]
-        L.pfd_interbasin_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_inflow_idxs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]
-        L.pfd_basin_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                       C.POINTER(C.c_int64), C.c_int]
-        L.pfd_subbasins_pfafstetter.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
-                                                C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
-                                                C.c_int]
-        L.pfd_subbasins_area.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                         C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.pfd_upscale.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                  C.c_void_p, C.c_int]
-        L.pfd_upscale_outlets.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                          C.c_int]
-        L.pfd_upscale_error.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
-        L.pfd_stream_distance_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
-        L.pfd_strahler_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                         C.POINTER(C.c_int64)]
-        L.pfd_hand_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                     C.c_void_p, C.POINTER(C.c_int64)]
-        L.pfd_verify_basins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-        L.pfd_verify_hand.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-        L.pfd_main_upstream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int]
-        L.pfd_upstream_sum.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_int]
-        L.pfd_stream_order_classic.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_stream_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_graph_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        L.pfd_verify_upstream_area_cell.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-        L.pfd_checksum_i32.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.pfd_basins_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.pfd_basins_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
-        L.pfd_fill_depressions.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_int,
-                                           C.c_double, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
-        L.pfd_ucat_area.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.pfd_ucat_volume.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                      C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
-        L.pfd_segment_length.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_segment_slope.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_double, C.c_void_p, C.c_int]
-        L.pfd_segment_average.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                          C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int]
-        L.pfd_segment_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                         C.c_void_p, C.c_double, C.c_void_p, C.c_int]
-        L.pfd_downstream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_moving_average.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                         C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_int]
-        L.pfd_moving_median.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                        C.c_double, C.c_void_p, C.c_int]
-        L.pfd_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                               C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
-        L.pfd_debug_window_wmax.argtypes = [C.c_int, C.POINTER(C.c_int)]
-        L.pfd_floodplains.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_snap_downstream.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
-        L.pfd_snap.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
-        L.pfd_raster_create_general.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.pfd_set_idxs_seq.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
-        L.pfd_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        L.pfd_last_timing.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t,
-                                      C.POINTER(C.c_int)]
-        L.pfd_comm_exchange_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.pfd_comm_allgather_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.pfd_set_block_io.argtypes = [C.c_void_p, C.c_int]
-        L.pfd_set_block_update.argtypes = [C.c_void_p, C.c_int]
-        L.pfd_malloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
-        L.pfd_free.argtypes = [C.c_int, C.c_void_p]
-        L.pfd_memcpy_h2d.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.pfd_memcpy_d2h.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.pfd_device_synchronize.argtypes = [C.c_int]
-        L.pfd_trim.argtypes = [C.c_int]
-        L.pfd_reserve.argtypes = [C.c_int, C.c_size_t]
-        L.pfd_alloc_stats.argtypes = [C.POINTER(C.c_int64)]
-        L.pfd_mem_info.argtypes = [C.c_int, C.POINTER(C.c_int64)]
-        L.pfd_transfer_stats.argtypes = [C.POINTER(C.c_double), C.c_int]
-        L.pfd_count_nonfinite.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.pfd_trib_info_block.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
-        L.pfd_device_count.argtypes = [C.POINTER(C.c_int)]
-        L.pfd_synth_d8.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
-                                   C.c_int64, C.c_int64, C.c_void_p]
-        L.pfd_synth_elev_f32.argtypes = L.pfd_synth_d8.argtypes
-        L.pfd_synth_weights_f32.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -235,6 +202,21 @@ def ptr(a):
     if isinstance(a, DeviceBuffer):
         return C.c_void_p(a.addr)
     return C.c_void_p(int(a))
+
+
+def _list_call(cap, alloc, call):
+    """The protocol of the list calls (csrc/lists.h): the C call reports the count and leaves the lists unwritten when
+    they do not fit ``cap`` entries; it is then made once more with room for exactly the count.  ``alloc(cap)`` returns
+    the output arrays for a capacity, ``call(cap, arrays)`` makes the C call and returns the reported count.  Returns
+    (arrays, count)."""
+    arrays = alloc(cap)
+    k = call(cap, arrays)
+    if k > cap:
+        cap, arrays = k, alloc(k)
+        k = call(cap, arrays)
+        if k > cap:
+            raise RuntimeError(f"a list call reported {cap} entries, then {k}")
+    return arrays, k
 
 
 def _payload_pair(a):
@@ -840,16 +822,13 @@ class RasterHandle:
         def run(cells, cap, offsets, dists, space):
             check(lib().pfd_path(self._h, ptr(idxs), k, int(direction), code, ptr(idxs_us_main), ptr(mask), ptr(tab), has_max,
                                  C.c_double(mx), ptr(cells), int(cap), ptr(offsets), ptr(dists), C.byref(m), space))
-        if memspace != PFD_HOST:
-            run(idxs_out, cap_idxs or 0, offsets_out, dist_out, memspace)
             return int(m.value)
-        cap = max(4096, 64 * k)
-        while True:
-            cells, offsets, dists = np.empty(cap, idx_dtype), np.zeros(k + 1, np.int64), np.zeros(k, np.float64)
-            run(cells, cap, offsets, dists, PFD_HOST)
-            if m.value <= cap:
-                return cells[:m.value].copy(), offsets, dists
-            cap = int(m.value)
+        if memspace != PFD_HOST:
+            return run(idxs_out, cap_idxs or 0, offsets_out, dist_out, memspace)
+        (cells, offsets, dists), n = _list_call(
+            max(4096, 64 * k), lambda cap: (np.empty(cap, idx_dtype), np.zeros(k + 1, np.int64), np.zeros(k, np.float64)),
+            lambda cap, a: run(a[0], cap, a[1], a[2], PFD_HOST))
+        return cells[:n].copy(), offsets, dists
 
     # -- outlets derived from the network (csrc/outlets.hip) ------------------------------------------------------
     def _outlet_cap(self):
@@ -862,44 +841,40 @@ class RasterHandle:
         """(int32 map[n], outlet cells[k]) of pfd_subbasins_streamorder.  PFD_DEVICE: ``strord``, ``out`` and ``idxs_out``
         (``cap`` entries) are DeviceBuffers; returns (out, idxs_out, k)."""
         k = C.c_int64(0)
+
+        def run(cap, idxs, space):
+            check(lib().pfd_subbasins_streamorder(self._h, int(dtype_code), ptr(strord), int(min_sto),
+                                                  IDX_CODE[np.dtype(idx_dtype)], ptr(idxs), int(cap), C.byref(k), ptr(out), space))
+            return int(k.value)
         if memspace != PFD_HOST:
-            check(lib().pfd_subbasins_streamorder(self._h, int(dtype_code), ptr(strord), int(min_sto),
-                                                  IDX_CODE[np.dtype(idx_dtype)], ptr(idxs_out), int(cap), C.byref(k), ptr(out),
-                                                  memspace))
-            return out, idxs_out, int(k.value)
+            return out, idxs_out, run(cap, idxs_out, memspace)
         out = np.empty(self.n, np.int32)
-        cap = self._outlet_cap() if cap is None else int(cap)
-        while True:
-            idxs = np.empty(cap, idx_dtype)
-            check(lib().pfd_subbasins_streamorder(self._h, int(dtype_code), ptr(strord), int(min_sto),
-                                                  IDX_CODE[np.dtype(idx_dtype)], ptr(idxs), cap, C.byref(k), ptr(out), PFD_HOST))
-            if k.value <= cap:
-                return out, idxs[:k.value].copy()
-            cap = int(k.value)
+        idxs, n = _list_call(self._outlet_cap() if cap is None else int(cap), lambda cap: np.empty(cap, idx_dtype),
+                             lambda cap, idxs: run(cap, idxs, PFD_HOST))
+        return out, idxs[:n].copy()
 
     def outflow_idxs(self, region, idx_dtype, cap=None):
         """Outflow cells of a uint8 region mask in forward sequence order (pfd_outflow_idxs)."""
         k = C.c_int64(0)
-        cap = self._outlet_cap() if cap is None else int(cap)
-        while True:
-            idxs = np.empty(cap, idx_dtype)
+
+        def run(cap, idxs):
             check(lib().pfd_outflow_idxs(self._h, ptr(region), IDX_CODE[np.dtype(idx_dtype)], ptr(idxs), cap, C.byref(k),
                                          PFD_HOST))
-            if k.value <= cap:
-                return idxs[:k.value].copy()
-            cap = int(k.value)
+            return int(k.value)
+        idxs, n = _list_call(self._outlet_cap() if cap is None else int(cap), lambda cap: np.empty(cap, idx_dtype), run)
+        return idxs[:n].copy()
 
     def basin_outlets(self, regions, dtype_code, idx_dtype, cap=None):
         """(labels[k] in the dtype of ``regions``, outlet cells[k]) sorted by label (pfd_basin_outlets)."""
         k = C.c_int64(0)
-        cap = self._outlet_cap() if cap is None else int(cap)
-        while True:
-            idxs, lbs = np.empty(cap, idx_dtype), np.empty(cap, regions.dtype)
-            check(lib().pfd_basin_outlets(self._h, int(dtype_code), ptr(regions), IDX_CODE[np.dtype(idx_dtype)], ptr(idxs),
-                                          ptr(lbs), cap, C.byref(k), PFD_HOST))
-            if k.value <= cap:
-                return lbs[:k.value].copy(), idxs[:k.value].copy()
-            cap = int(k.value)
+
+        def run(cap, a):
+            check(lib().pfd_basin_outlets(self._h, int(dtype_code), ptr(regions), IDX_CODE[np.dtype(idx_dtype)], ptr(a[0]),
+                                          ptr(a[1]), cap, C.byref(k), PFD_HOST))
+            return int(k.value)
+        (idxs, lbs), n = _list_call(self._outlet_cap() if cap is None else int(cap),
+                                    lambda cap: (np.empty(cap, idx_dtype), np.empty(cap, regions.dtype)), run)
+        return lbs[:n].copy(), idxs[:n].copy()
 
     # -- the rest of the BASINS section (csrc/basins_ext.hip) ---------------------------------------------------------
     def interbasin_mask(self, region, stream):
@@ -911,40 +886,39 @@ class RasterHandle:
     def inflow_idxs(self, region, idx_dtype, cap=None):
         """Inflow cells of a uint8 region mask in reversed sequence order (pfd_inflow_idxs)."""
         k = C.c_int64(0)
-        cap = self._outlet_cap() if cap is None else int(cap)
-        while True:
-            idxs = np.empty(cap, idx_dtype)
+
+        def run(cap, idxs):
             check(lib().pfd_inflow_idxs(self._h, ptr(region), IDX_CODE[np.dtype(idx_dtype)], ptr(idxs), cap, C.byref(k),
                                         PFD_HOST))
-            if k.value <= cap:
-                return idxs[:k.value].copy()
-            cap = int(k.value)
+            return int(k.value)
+        idxs, n = _list_call(self._outlet_cap() if cap is None else int(cap), lambda cap: np.empty(cap, idx_dtype), run)
+        return idxs[:n].copy()
 
     def basin_bounds(self, labels, dtype_code, cap=None):
         """(sorted unique labels[k] > 0, int64 [4, k] = row_min, row_max, col_min, col_max) of pfd_basin_bounds."""
         k = C.c_int64(0)
-        cap = 4096 if cap is None else int(cap)
-        while True:
-            lbs, bounds = np.empty(cap, labels.dtype), np.empty(4 * cap, np.int64)
-            check(lib().pfd_basin_bounds(self._h, int(dtype_code), ptr(labels), ptr(lbs), ptr(bounds), cap, C.byref(k), PFD_HOST))
-            if k.value <= cap:
-                return lbs[:k.value].copy(), bounds[:4 * k.value].reshape(4, k.value).copy()
-            cap = int(k.value)
+
+        def run(cap, a):
+            check(lib().pfd_basin_bounds(self._h, int(dtype_code), ptr(labels), ptr(a[0]), ptr(a[1]), cap, C.byref(k), PFD_HOST))
+            return int(k.value)
+        (lbs, bounds), n = _list_call(4096 if cap is None else int(cap),
+                                      lambda cap: (np.empty(cap, labels.dtype), np.empty(4 * cap, np.int64)), run)
+        return lbs[:n].copy(), bounds[:4 * n].reshape(4, n).copy()
 
     def subbasins_pfafstetter(self, uparea, dtype_code, upa_min, depth, idxs_us_main, idxs_pit, idx_dtype, cap=None):
         """(int32 map[n], outlet cells[k]) of pfd_subbasins_pfafstetter; ``uparea`` / ``idxs_us_main`` (int64) may be None."""
         k = C.c_int64(0)
         out = np.empty(self.n, np.int32)
         idxs_pit = np.ascontiguousarray(idxs_pit, dtype=np.int64)
-        cap = idxs_pit.size + max(1 << 16, 16 * idxs_pit.size) if cap is None else int(cap)
-        while True:
-            idxs = np.empty(cap, idx_dtype)
+
+        def run(cap, idxs):
             check(lib().pfd_subbasins_pfafstetter(self._h, int(dtype_code), ptr(uparea), float(upa_min), int(depth),
                                                   ptr(idxs_us_main), ptr(idxs_pit), idxs_pit.size, IDX_CODE[np.dtype(idx_dtype)],
                                                   ptr(idxs), cap, C.byref(k), ptr(out), PFD_HOST))
-            if k.value <= cap:
-                return out, idxs[:k.value].copy()
-            cap = int(k.value)
+            return int(k.value)
+        idxs, n = _list_call(idxs_pit.size + max(1 << 16, 16 * idxs_pit.size) if cap is None else int(cap),
+                             lambda cap: np.empty(cap, idx_dtype), run)
+        return out, idxs[:n].copy()
 
     def subbasins_area(self, uparea, dtype_code, area_min, compare, idxs_us_main, idx_dtype, cap=None, flags=0, out=None,
                        idxs_out=None, memspace=PFD_HOST):
@@ -954,21 +928,18 @@ class RasterHandle:
         k = C.c_int64(0)
         stats = np.zeros(4, np.int64)
         icode = IDX_CODE[np.dtype(idx_dtype)]
+
+        def run(cap, idxs, space):
+            check(lib().pfd_subbasins_area(self._h, int(dtype_code), ptr(uparea), float(area_min), int(compare),
+                                           ptr(idxs_us_main), icode, ptr(idxs), int(cap), C.byref(k), ptr(out), ptr(stats),
+                                           int(flags), space))
+            return int(k.value)
         if memspace != PFD_HOST:
-            check(lib().pfd_subbasins_area(self._h, int(dtype_code), ptr(uparea), float(area_min), int(compare),
-                                           ptr(idxs_us_main), icode, ptr(idxs_out), int(cap), C.byref(k), ptr(out), ptr(stats),
-                                           int(flags), memspace))
-            return out, idxs_out, int(k.value), stats
+            return out, idxs_out, run(cap, idxs_out, memspace), stats
         out = np.empty(self.n, np.uint32)
-        cap = self._outlet_cap() if cap is None else int(cap)
-        while True:
-            idxs = np.empty(cap, idx_dtype)
-            check(lib().pfd_subbasins_area(self._h, int(dtype_code), ptr(uparea), float(area_min), int(compare),
-                                           ptr(idxs_us_main), icode, ptr(idxs), cap, C.byref(k), ptr(out), ptr(stats),
-                                           int(flags), PFD_HOST))
-            if k.value <= cap:
-                return out, idxs[:k.value].copy(), stats
-            cap = int(k.value)
+        idxs, n = _list_call(self._outlet_cap() if cap is None else int(cap), lambda cap: np.empty(cap, idx_dtype),
+                             lambda cap, idxs: run(cap, idxs, PFD_HOST))
+        return out, idxs[:n].copy(), stats
 
     # -- upscaling (csrc/upscale.hip) ------------------------------------------------------------------------------------
     def upscale(self, method, cellsize, uparea, effarea, idx_dtype, outlets_only=False):
@@ -1204,8 +1175,7 @@ def synth_mosaic_device(base: np.ndarray, nrow, ncol, device=0):
     """A host base raster tiled over nrow x ncol cells in HBM (nodata frame per copy): pfd_synth_mosaic."""
     base = np.ascontiguousarray(base, dtype=np.uint8)
     buf = DeviceBuffer(int(nrow) * int(ncol), device)
-    check(lib().pfd_synth_mosaic(device, ptr(base), C.c_int64(base.shape[0]), C.c_int64(base.shape[1]), C.c_int64(nrow),
-                                 C.c_int64(ncol), C.c_void_p(buf.addr)))
+    check(lib().pfd_synth_mosaic(device, ptr(base), base.shape[0], base.shape[1], int(nrow), int(ncol), C.c_void_p(buf.addr)))
     return buf
 
 

@@ -220,3 +220,15 @@ def test_basins_ext_errors_and_dtypes(gpu_lib):
     assert "idxs_us_main" in cached._cached
     for a, b in zip(cached.subbasins_pfafstetter(depth=2), flw.subbasins_pfafstetter(depth=2)):
         assert _same(a, b)
+
+
+def test_pfafstetter_second_lap(gpu_lib):
+    """An outlet list longer than the first call's room (cap=1 on the 5 x 7 raster: 4 outlets): the binding repeats the
+    call with room for all, and gives the default capacity's map and list."""
+    from pyflwdir_amd import _hip
+
+    flw = _flw(BC.d8_of("synth_tiny_5x7"))
+    upa_min = BC.threshold(flw.upstream_area())
+    sub, idxs = flw.subbasins_pfafstetter(depth=1, upa_min=upa_min)
+    s2, i2 = flw._h.subbasins_pfafstetter(None, _hip.PFD_I32, upa_min, 1, None, flw.idxs_pit, idxs.dtype, cap=1)
+    assert idxs.size >= 2 and _same(s2.reshape(sub.shape), sub) and _same(i2, idxs)

@@ -215,6 +215,24 @@ def test_outlets_errors_and_dtypes(gpu_lib):
     assert _same(got[1], flw.subbasins_streamorder(strord=strord, min_sto=1)[1]) and got[1].size > 3
 
 
+def test_outflow_and_basin_outlets_second_lap(gpu_lib):
+    """Lists longer than the first call's room (cap=1 on the 5 x 7 raster: 4 outflow cells of the blob region, 4 basin
+    outlets): the binding repeats the call with room for all, and gives the default capacity's arrays."""
+    import pyflwdir_amd as pyflwdir
+
+    _hip = pyflwdir._hip
+    d8 = np.load(os.path.join(GOLD, "synth_tiny_5x7.npz"))["d8"]
+    flw = pyflwdir.from_array(d8, ftype="d8", check_ftype=False, cache=False)
+    blob = OC.region(d8.shape, "blob")
+    want = flw.outflow_idxs(blob)
+    got = flw._h.outflow_idxs(np.ascontiguousarray(blob).view(np.uint8), want.dtype, cap=1)
+    assert want.size >= 2 and _same(got, want)
+    basins = np.ascontiguousarray(flw.basins().astype(np.int32))
+    lbs, idxs = flw.basin_outlets(basins)
+    l2, i2 = flw._h.basin_outlets(basins, _hip.PFD_I32, idxs.dtype, cap=1)
+    assert lbs.size >= 2 and _same(l2, lbs) and _same(i2, idxs)
+
+
 def test_outlets_device_memory_and_transfers(gpu_lib):
     """pfd_subbasins_streamorder with stream order, map and list in device memory (PFD_DEVICE) gives the host call's
     bytes; a host call moves the stream order up and the map and the list down — never the sequence."""

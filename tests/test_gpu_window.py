@@ -115,6 +115,24 @@ def test_path_from_xy_and_single_start(gpu_lib, G):
     assert [q.tolist() for q in p] == [[int(s)] for s in starts] and np.all(d == 0.0)
 
 
+def test_path_longer_than_the_first_capacity(gpu_lib):
+    """One path of 5000 cells (a row draining east into a pit in its last column) against the 4096 cells a first call
+    with one start cell has room for: the binding repeats the call with room for all."""
+    import pyflwdir_amd as pyflwdir
+    from pyflwdir_amd import _hip
+
+    res = {}
+    for n in (100, 5000):
+        d8 = np.full((1, n), 1, np.uint8)  # (1: east)
+        d8[0, -1] = 0
+        flw = pyflwdir.from_array(d8, ftype="d8", check_ftype=False, cache=False)
+        res[n] = flw._h.path(np.array([0]), _hip.PFD_DOWN, np.int32)
+        cells, offsets, dists = res[n]
+        assert cells.dtype == np.int32 and np.array_equal(cells, np.arange(n)) and offsets.tolist() == [0, n]
+        assert dists.dtype == np.float64 and dists.shape == (1,)
+    assert res[100][2][0] == 99.0 and res[5000][2][0] == res[100][2][0] / 99 * 4999  # (cells: one per step)
+
+
 def test_cabi_with_device_inputs_and_outputs(gpu_lib, G):
     """One case per entry point with the per-cell inputs and the results in device memory."""
     from pyflwdir_amd import _hip

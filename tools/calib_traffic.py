@@ -4,7 +4,6 @@ import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyflwdir_amd import _hip
 L = _hip.lib()
-L.pfd_calib_traffic.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
 N = 2 << 30
 buf = _hip.DeviceBuffer(N)
 for w in (1, 4, 8, 16):
