@@ -895,8 +895,14 @@ struct FillDown {
   __device__ __forceinline__ Elem pre_post(u32 child) const {
     u32 c = ncode[child];
     if (c == D8_HALO) {  // (a halo cell of a row block: its direction is in the given codes)
-      const u32 row = geo_row(g, child);
-      c = halo_raw[(row == 0 ? 0u : g.ncol) + (child - row * g.ncol)];
+      const u32 row = geo_row(g, child), col = child - row * g.ncol;
+      c = halo_raw[(row == 0 ? 0u : g.ncol) + col];
+      // A PADDING slot carries cell 0 (exact.hip), which in a block with a top halo row is a halo cell whatever its code
+      // as given: a step that does not lead into the own rows (north out of row 0, west out of column 0) would index
+      // `data` before its first element.  Only a step into the own rows links a halo cell to the block (k_plan_tile),
+      // so any other code is a padding slot's, whose element is never folded.
+      const int k = d8_is_dir(c) ? d8_slot(c) : 0;
+      if (!d8_is_dir(c) || d8_dr(k) != (row == 0 ? 1 : -1) || col + (u32)d8_dc(k) >= g.ncol) return Elem{out[child], 0u};
     }
     return Elem{out[child], r.isnd(data[d8_down(g, child, c)]) ? 0u : 1u};
   }
