@@ -12,6 +12,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -189,11 +191,6 @@ struct pfd_raster {
   size_t bytes_held = 0;
   void *pending = nullptr;  // split-phase multi-block pass in flight (dist.hip)
   void *pending_basins = nullptr;  // split-phase multi-block basins query in flight (paths.hip)
-  // row blocks, exact-order up-sweeps: the given values of the halo rows (2 * ncol elements, device) are put back into
-  // the result right after the tile pass has written every cell (run_exact_up); set by the caller around the sweep
-  const void *xseed = nullptr;
-  void *xseed_out = nullptr;
-  size_t xseed_elem = 0;
   int block_update = 0;  // pfd_set_block_update: 0 = block up-sweeps keep nothing, 1 = keep the sweep for updates, 2 = update
   int block_seed_space = PFD_HOST;  // where the pfd_*_block entry points read their halo seeds (pfd_set_block_io)
   u8 *halo_raw = nullptr;  // row blocks: the D8 codes of the two halo rows as given (2 * ncol; the normalised codes hold sinks there)
@@ -235,6 +232,49 @@ struct DevBuf {
   DevBuf(const DevBuf &) = delete;
   DevBuf &operator=(const DevBuf &) = delete;
 };
+// A device array that its holder owns (the arrays of the exact-order plan, exact.h): it reads as a T *, is released with
+// its holder, and its bytes count in the handle's bytes_held for as long as it lives.
+template <class T>
+struct DevArr {
+  T *p = nullptr;
+  size_t bytes = 0;
+  size_t *held = nullptr;  // the bytes_held of the handle it was allocated for (which outlives it)
+  DevArr() {}
+  ~DevArr() { release(); }
+  int alloc(pfd_raster *h, size_t nbytes) {
+    release();
+    PFDCHK(pfd_dmalloc((void **)&p, nbytes));
+    bytes = nbytes, held = &h->bytes_held;
+    *held += bytes;
+    return PFD_OK;
+  }
+  void release() {
+    if (!p) return;
+    pfd_dfree(p);
+    *held -= std::min(*held, bytes);
+    p = nullptr, bytes = 0;
+  }
+  operator T *() const { return p; }
+  DevArr(const DevArr &) = delete;
+  DevArr &operator=(const DevArr &) = delete;
+};
+// The scratch of a rocprim call.  call(p, bytes) -> hipError_t is the rocprim call with its first two arguments left open:
+// asked for its size with p == nullptr, then run in `tmp`.  The caller owns `tmp`, and with it the moment the scratch is
+// released (pfd_dfree waits for the stream).  pfd_rocprim_scratch stops after the allocation: for a call that runs several
+// times in one scratch (the piecewise sort of subgrid.hip).
+template <class Call>
+static int pfd_rocprim_scratch(DevBuf &tmp, Call call, size_t *bytes) {
+  *bytes = 0;
+  HIPCHK(call(nullptr, *bytes));
+  return tmp.alloc(std::max<size_t>(*bytes, 16));
+}
+template <class Call>
+static int pfd_rocprim(DevBuf &tmp, Call call) {
+  size_t bytes = 0;
+  PFDCHK(pfd_rocprim_scratch(tmp, call, &bytes));
+  HIPCHK(call(tmp.p, bytes));
+  return PFD_OK;
+}
 
 // Host <-> device traffic of the calling thread's API calls (pfd_transfer_stats, api.hip).
 struct PfdTransfer {

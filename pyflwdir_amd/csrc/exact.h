@@ -48,23 +48,23 @@ __host__ __device__ inline bool xl_trunk(u32 m) { return (m & 0xF8u) == XL_TRUNK
 
 struct ExactPlan {
   u32 ntr = 0, ntc = 0;
-  u8 *lh = nullptr;       // [n] leaf step (0..XCAP), XL_TRUNK + post slots, XL_NODATA, XL_HALO
-  u8 *kids = nullptr;     // [n] mask of the neighbour slots draining into the cell
-  uint16_t *tord = nullptr;  // [ntiles * 4096] leaf cells of the tile, ordered by step: local index | downstream slot << 12 | pit << 15
-  uint16_t *toff = nullptr;  // [ntiles * XOFF] start of step s in tord; entries past the last step = total
-  u32 *cslot = nullptr;   // [n] slot of a trunk cell (its real slot; post slots follow it); undefined elsewhere
+  DevArr<u8> lh;          // [n] leaf step (0..XCAP), XL_TRUNK + post slots, XL_NODATA, XL_HALO
+  DevArr<u8> kids;        // [n] mask of the neighbour slots draining into the cell
+  DevArr<uint16_t> tord;  // [ntiles * 4096] leaf cells of the tile, ordered by step: local index | downstream slot << 12 | pit << 15
+  DevArr<uint16_t> toff;  // [ntiles * XOFF] start of step s in tord; entries past the last step = total
+  DevArr<u32> cslot;      // [n] slot of a trunk cell (its real slot; post slots follow it); undefined elsewhere
   // The trunk cells of every 64 x 64 tile as a dense list (round 5): {slot, local index | post slots << 12}.  The passes
   // that visit the trunk cells tile by tile (k_xtrunk_demit_list, k_xtrunk_unscatter_list) read 8 contiguous bytes per
   // trunk cell instead of the marks of every cell plus 4 scattered bytes of cslot per trunk cell — a quarter of the
   // cells, one or two per 64-byte sector along a river.
-  uint2 *tlist = nullptr;  // [ntrunk]
-  u32 *tl_off = nullptr;   // [ntiles + 1] first entry of the tile
-  u32 *scell = nullptr;   // [nslot]
-  uint16_t *sinfo = nullptr;  // [nslot]
-  u32 *spost = nullptr;   // [nslot / 32 + 4] bit s = slot s is a post slot (what the serial fold needs of sinfo)
-  u32 *cstart = nullptr;  // [nchain] first slot of the chain (a multiple of 4: chains are padded)
-  u32 *clen = nullptr;    // [nchain] slots in the chain | post slots behind its last cell << 29
-  u32 *longc = nullptr;   // [nlong] ids of the chains of >= XLONG slots, ascending (= by round)
+  DevArr<uint2> tlist;    // [ntrunk]
+  DevArr<u32> tl_off;     // [ntiles + 1] first entry of the tile
+  DevArr<u32> scell;      // [nslot]
+  DevArr<uint16_t> sinfo; // [nslot]
+  DevArr<u32> spost;      // [nslot / 32 + 4] bit s = slot s is a post slot (what the serial fold needs of sinfo)
+  DevArr<u32> cstart;     // [nchain] first slot of the chain (a multiple of 4: chains are padded)
+  DevArr<u32> clen;       // [nchain] slots in the chain | post slots behind its last cell << 29
+  DevArr<u32> longc;      // [nlong] ids of the chains of >= XLONG slots, ascending (= by round)
   i64 nlong = 0;
   i64 b_long[33] = {0};   // long chains of round b = longc[b_long[b] .. b_long[b+1])
   u32 b_maxlen[32] = {0}; // slots of the longest chain of round b (0: no chain of XLONG slots or more)
@@ -73,20 +73,18 @@ struct ExactPlan {
   i64 nslot = 0, nchain = 0, ntrunk = 0;
   i64 b_chain[33] = {0};  // chains of round b = [b_chain[b], b_chain[b+1])
   i64 b_slot[33] = {0};   // slots  of round b = [b_slot[b],  b_slot[b+1])
-  size_t bytes = 0;
   // ---- incremental re-sweeps of a row block (run_exact_up, pfd_set_block_update) ------------------------------
   // A block's up-sweep is repeated with other halo seeds until the boundary rows settle; from the second sweep on
   // only the chains below a CHANGED seed are folded again: the element / value arrays of the last sweep are kept,
   // a chain is dirty when a halo cell with another seed drains into it, or when the chain that ends in it was dirty.
-  u32 *schain = nullptr;  // [nslot] chain of a slot (built on first use)
-  u32 *dchain = nullptr;  // [nchain] chain of the cell the chain's last cell drains into (0xFFFFFFFF: none)
-  u32 *hfeed = nullptr;   // [2 * ncol] chain of the own cell a halo cell drains into (0xFFFFFFFF: none)
-  u8 *dirty = nullptr;    // [nchain]
+  DevArr<u32> schain;     // [nslot] chain of a slot (built on first use)
+  DevArr<u32> dchain;     // [nchain] chain of the cell the chain's last cell drains into (0xFFFFFFFF: none)
+  DevArr<u32> hfeed;      // [2 * ncol] chain of the own cell a halo cell drains into (0xFFFFFFFF: none)
+  DevArr<u8> dirty;       // [nchain]
   bool xinc_ready = false;    // the four maps above are built AND checked (pfd_xinc_prepare)
   bool xinc_refused = false;  // they cannot be: a halo cell drains into a non-trunk cell of this plan
-  size_t xinc_map_bytes = 0;
-  void *incE = nullptr, *incR = nullptr, *incSeed = nullptr;
-  size_t inc_tag = 0, inc_bytes = 0;  // operation of the kept sweep (type hash); bytes of incE + incR + incSeed
+  DevArr<void> incE, incR, incSeed;  // the kept sweep: its element and value arrays, the halo seeds it ran with
+  size_t inc_tag = 0;                // its operation (type hash)
   const void *inc_out = nullptr;      // its result buffer
   bool inc_valid = false;
 };
@@ -102,12 +100,21 @@ inline int xplan_tail_split(const ExactPlan *p) {
   if ((p->nslot - p->b_slot[b2]) * 8 > p->nslot) return -1;
   return b2;
 }
+// the halo seeds of a row block's up-sweep (run_exact_up): the 2 * ncol given values of the halo rows (device, `elem` bytes
+// each) and the result buffer whose halo rows they go back into right after the tile pass has written every cell
+struct XSeeds {
+  const void *dev = nullptr;
+  void *out = nullptr;
+  size_t elem = 0;
+  explicit operator bool() const { return dev && out; }  // (none: a whole raster)
+};
 int pfd_xinc_prepare(pfd_raster *h);  // builds schain / dchain / hfeed / dirty (once per plan)
 void pfd_xinc_drop(pfd_raster *h);    // releases the kept sweep (incE / incR / incSeed)
 int pfd_xinc_mark(pfd_raster *h, const void *seed_dev, size_t elem);  // dirty <- chains below a changed seed; keeps the seeds
 
-// builds the plan on first use; h->xplan_state: 0 not built, 1 ready, -1 not available (cycles, row
-// block, more than 2^32 - 2 cells)
+// builds the plan on first use (exact.hip: xplan_eligible, XplanBuild); h->xplan_state: 0 not built, 1 ready, -1 not
+// available (cycles, a row block without its halo codes, more than 2^32 - 2 cells, ...).  The plan owns its device arrays
+// (DevArr, common.h): pfd_free_xplan deletes it, and the handle's bytes_held follows every array from allocation to release
 int pfd_ensure_xplan(pfd_raster *h, bool allow_block = false);
 void pfd_free_xplan(pfd_raster *h);
 

@@ -17,8 +17,6 @@
 #include "exact.h"
 #include "tiled.h"
 
-int pfd_path_rank(pfd_raster *h, const u8 *codes, u32 *out_dev, int *complete);                         // paths.hip
-int pfd_path_labels(pfd_raster *h, const u8 *codes, const u32 *seed_dev, u32 *out_dev, int *complete);  // paths.hip
 int pfd_path_rank_tails(pfd_raster *h, const u8 *codes, u32 *hops_dev, u32 *tails_dev, int *complete);   // paths.hip
 
 // ---------------------------------------------------------------------------------------------
@@ -823,21 +821,13 @@ __global__ void __launch_bounds__(256) k_xinc_mark(const W *__restrict__ seed, W
 void pfd_xinc_drop(pfd_raster *h) {
   ExactPlan *p = (ExactPlan *)h->xplan;
   if (!p) return;
-  pfd_dfree(p->incE);
-  pfd_dfree(p->incR);
-  pfd_dfree(p->incSeed);
-  p->incE = p->incR = p->incSeed = nullptr;
-  h->bytes_held -= std::min(h->bytes_held, p->inc_bytes);
-  p->inc_bytes = 0;
+  p->incE.release(), p->incR.release(), p->incSeed.release();
   p->inc_valid = false;
   p->inc_out = nullptr;
 }
 // releases the static maps of the incremental sweeps (a failed or half-run prepare must not look like a finished one)
-static void xinc_free_maps(pfd_raster *h, ExactPlan *p) {
-  pfd_dfree(p->schain), pfd_dfree(p->dchain), pfd_dfree(p->hfeed), pfd_dfree(p->dirty);
-  p->schain = p->dchain = p->hfeed = nullptr, p->dirty = nullptr;
-  p->bytes -= std::min(p->bytes, p->xinc_map_bytes), h->bytes_held -= std::min(h->bytes_held, p->xinc_map_bytes);
-  p->xinc_map_bytes = 0;
+static void xinc_free_maps(ExactPlan *p) {
+  p->schain.release(), p->dchain.release(), p->hfeed.release(), p->dirty.release();
   p->xinc_ready = false;
 }
 static int xinc_build_maps(pfd_raster *h, ExactPlan *p, size_t nsl, size_t nch, u64 *odd) {
@@ -869,27 +859,23 @@ int pfd_xinc_prepare(pfd_raster *h) {
     pfd_set_error("incremental block sweeps: a halo cell drains into a cell that is not a trunk cell of the block's plan");
     return PFD_EUNSUPPORTED;
   }
-  xinc_free_maps(h, p);  // (whatever an earlier, failed attempt left)
+  xinc_free_maps(p);  // (whatever an earlier, failed attempt left)
   const size_t nsl = std::max<size_t>((size_t)p->nslot, 4), nch = std::max<size_t>((size_t)p->nchain, 1);
   int rc;
-  if ((rc = pfd_dmalloc((void **)&p->schain, nsl * sizeof(u32))) != PFD_OK ||
-      (rc = pfd_dmalloc((void **)&p->dchain, nch * sizeof(u32))) != PFD_OK ||
-      (rc = pfd_dmalloc((void **)&p->hfeed, 2 * (size_t)h->ncol * sizeof(u32))) != PFD_OK ||
-      (rc = pfd_dmalloc((void **)&p->dirty, nch)) != PFD_OK) {
-    xinc_free_maps(h, p);
+  if ((rc = p->schain.alloc(h, nsl * sizeof(u32))) != PFD_OK || (rc = p->dchain.alloc(h, nch * sizeof(u32))) != PFD_OK ||
+      (rc = p->hfeed.alloc(h, 2 * (size_t)h->ncol * sizeof(u32))) != PFD_OK || (rc = p->dirty.alloc(h, nch)) != PFD_OK) {
+    xinc_free_maps(p);
     return rc;
   }
-  p->xinc_map_bytes = nsl * 4 + nch * 5 + 2 * (size_t)h->ncol * 4;
-  p->bytes += p->xinc_map_bytes, h->bytes_held += p->xinc_map_bytes;
   u64 odd = 0;
   rc = xinc_build_maps(h, p, nsl, nch, &odd);
   if (rc != PFD_OK) {
     (void)hipStreamSynchronize(h->stream);  // (nothing may still write the maps when they are freed)
-    xinc_free_maps(h, p);
+    xinc_free_maps(p);
     return rc;
   }
   if (odd) {
-    xinc_free_maps(h, p);
+    xinc_free_maps(p);
     p->xinc_refused = true;
     pfd_set_error("internal: %llu halo cells drain into a cell that is not a trunk cell of the block's plan", (unsigned long long)odd);
     return PFD_EUNSUPPORTED;
@@ -902,9 +888,9 @@ int pfd_xinc_mark(pfd_raster *h, const void *seed_dev, size_t elem) {
   const u32 n2 = 2u * (u32)h->ncol;
   HIPCHK(hipMemsetAsync(p->dirty, 0, std::max<size_t>((size_t)p->nchain, 1), h->stream));
   const u32 grid = cdiv_u32(n2, 256);
-  if (elem == 1) k_xinc_mark<u8><<<grid, 256, 0, h->stream>>>((const u8 *)seed_dev, (u8 *)p->incSeed, p->hfeed, n2, p->dirty);
-  else if (elem == 4) k_xinc_mark<u32><<<grid, 256, 0, h->stream>>>((const u32 *)seed_dev, (u32 *)p->incSeed, p->hfeed, n2, p->dirty);
-  else if (elem == 8) k_xinc_mark<u64><<<grid, 256, 0, h->stream>>>((const u64 *)seed_dev, (u64 *)p->incSeed, p->hfeed, n2, p->dirty);
+  if (elem == 1) k_xinc_mark<u8><<<grid, 256, 0, h->stream>>>((const u8 *)seed_dev, (u8 *)p->incSeed.p, p->hfeed, n2, p->dirty);
+  else if (elem == 4) k_xinc_mark<u32><<<grid, 256, 0, h->stream>>>((const u32 *)seed_dev, (u32 *)p->incSeed.p, p->hfeed, n2, p->dirty);
+  else if (elem == 8) k_xinc_mark<u64><<<grid, 256, 0, h->stream>>>((const u64 *)seed_dev, (u64 *)p->incSeed.p, p->hfeed, n2, p->dirty);
   else {
     pfd_set_error("incremental block sweep: element size %zu", elem);
     return PFD_EINVAL;
@@ -914,343 +900,344 @@ int pfd_xinc_mark(pfd_raster *h, const void *seed_dev, size_t elem) {
 }
 
 void pfd_free_xplan(pfd_raster *h) {
-  ExactPlan *p = (ExactPlan *)h->xplan;
-  if (p) {
-    pfd_xinc_drop(h);
-    pfd_dfree(p->schain);
-    pfd_dfree(p->dchain);
-    pfd_dfree(p->hfeed);
-    pfd_dfree(p->dirty);
-    pfd_dfree(p->lh);
-    pfd_dfree(p->kids);
-    pfd_dfree(p->tord);
-    pfd_dfree(p->toff);
-    pfd_dfree(p->cslot);
-    pfd_dfree(p->tlist);
-    pfd_dfree(p->tl_off);
-    pfd_dfree(p->scell);
-    pfd_dfree(p->sinfo);
-    pfd_dfree(p->spost);
-    pfd_dfree(p->cstart);
-    pfd_dfree(p->clen);
-    pfd_dfree(p->longc);
-    h->bytes_held -= std::min(h->bytes_held, p->bytes);
-    delete p;
-  }
+  delete (ExactPlan *)h->xplan;  // (its arrays go with it, and leave the handle's bytes_held)
   h->xplan = nullptr;
   h->xplan_state = 0;
 }
 
-int pfd_ensure_xplan(pfd_raster *h, bool allow_block) {
-  if ((h->halo_top || h->halo_bot) && !allow_block) return pfd_require_whole(h, "the exact-order plan");
-  if (h->xplan_state != 0) return PFD_OK;
-  h->xplan_state = -1;
-  if (h->gen) return PFD_OK;
-  if (h->n > 4294967294ll || pfd_knob("PFD_EXACT_LEVELS")) return PFD_OK;
-  const bool block = h->halo_top || h->halo_bot;
-  // (row blocks: the cells of the halo rows hold given values, see k_plan_tile; the codes of the halo rows as given
-  //  must still be around)
-  if (block && (!h->halo_raw || pfd_knob("PFD_BLOCK_LEVELS"))) return PFD_OK;
-  if (h->acyclic < 0) return PFD_OK;
-  const u32 n = h->geo.n;
-  const u32 ntr = cdiv_u32((u64)h->nrow, XT), ntc = cdiv_u32((u64)h->ncol, XT);
-  const size_t ntiles = (size_t)ntr * ntc;
-  if (ntr > 65535u) return PFD_OK;
-  pfd_seg_begin(h, "exact_plan");
-  DevBuf upa;
-  PFDCHK(upa.alloc((size_t)n * sizeof(u32)));
-  int complete = 0;
-  {
-    const bool prof = h->profiling;  // (the tiled pass records its own segments: keep ours intact)
-    h->profiling = false;
+// ---------------------------------------------------------------------------------------------
+// The build of a plan: the steps of pfd_ensure_xplan, in the order run() takes them, and the scratch they share.
+// Every scratch buffer is a member and lives until the build ends (releasing a block waits for the stream, and moves
+// what the allocator hands out next), but for the two that the build's peak memory depends on: hcode goes after the
+// list of chain ends, upa — which holds that list from then on — after the round histogram.
+// ---------------------------------------------------------------------------------------------
+struct XIsLong {  // flag of a chain that a whole wave folds
+  __device__ bool operator()(u32 cl) const { return (cl & XC_LEN) >= XLONG; }
+};
+template <class T>
+struct Scratch : DevBuf {  // a DevBuf that reads as a T *
+  operator T *() const { return (T *)p; }
+};
+struct XplanBuild {
+  pfd_raster *const h;
+  const bool block;
+  const u32 n, ntr, ntc;
+  const size_t ntiles;  // (the chain-end count / list kernels: a 64 x 64 tile per workgroup)
+  ExactPlan *p = nullptr;
+  u32 nt32 = 0;              // chain ends = chains
+  u64 nchain = 0, npos = 0;  // chains (= nt32); positions = trunk cells
+  size_t nc1 = 1;            // max(nchain, 1)
+  u32 *tails = nullptr;       // the list of chain ends (in upa's buffer)
+  const u32 *depth = nullptr;  // light cells below a chain (dA or dB)
+  Scratch<u32> upa, tidx_at, hops, tailnum, bcount, cnt, dA, dB, pA, pB, parb, len_of, rank_of;
+  Scratch<u32> keys, keys2, iota, cj, adj, ctail, cpos, clenp, cpad, w, pend, pick;
+  Scratch<u8> hcode;
+  Scratch<uint16_t> hinfo;
+  Scratch<uint4> ucell;
+  DevBuf tmp;  // of the rocprim calls
+
+  explicit XplanBuild(pfd_raster *h_)
+      : h(h_), block(h_->halo_top || h_->halo_bot), n(h_->geo.n), ntr(cdiv_u32((u64)h_->nrow, XT)),
+        ntc(cdiv_u32((u64)h_->ncol, XT)), ntiles((size_t)ntr * ntc) {}
+
+  // exclusive scan of `count` u32 (in place where in == out); the scratch is `tmp`, kept until the next rocprim call
+  template <class In>
+  int scan(In in, u32 *out, size_t count) {
+    return pfd_rocprim(tmp, [&](void *t, size_t &b) {
+      return rocprim::exclusive_scan(t, b, in, out, 0u, count, rocprim::plus<u32>(), h->stream);
+    });
+  }
+
+  template <class... B>
+  static int allocs(size_t bytes, B &...bufs) {  // the same size for every one of them, in this order
+    int rc = PFD_OK;
+    ((rc = rc != PFD_OK ? rc : bufs.alloc(bytes)), ...);
+    return rc;
+  }
+
+  // weights of the heavy links: the upstream cells of every cell, by the tiled count — which also finds cycles
+  int weights(int *complete) {
+    PFDCHK(upa.alloc((size_t)n * sizeof(u32)));
     // (a row block: the count inside the block, nothing entering from the neighbours — the heavy links only need SOME
     //  consistent weight; the result covers the own rows, the halo rows stay 0 and are never heavy)
     if (block) HIPCHK(hipMemsetAsync(upa.p, 0, (size_t)n * sizeof(u32), h->stream));
-    const int rc = pfd_upstream_area_cell_tiled(h, (i32 *)upa.p + (size_t)h->halo_top * (size_t)h->ncol, &complete);
+    const bool prof = h->profiling;  // (the tiled pass records its own segments: keep ours intact)
+    h->profiling = false;
+    const int rc = pfd_upstream_area_cell_tiled(h, (i32 *)upa.p + (size_t)h->halo_top * (size_t)h->ncol, complete);
     h->profiling = prof;
     PFDCHK(rc);
-  }
-  if (!complete) {  // cycles: the level engine keeps the reference's semantics for them
-    h->acyclic = -1;
-    pfd_seg_end(h, 0);
+    h->acyclic = *complete ? 1 : -1;  // (cycles: the level engine keeps the reference's semantics for them)
     return PFD_OK;
   }
-  h->acyclic = 1;
-  ExactPlan *p = new ExactPlan();
-  h->xplan = p;  // (freed by pfd_free_xplan also when a later step fails)
-  p->ntr = ntr;
-  p->ntc = ntc;
-  int rc = PFD_OK;
-  auto fail = [&](int code) {
-    pfd_free_xplan(h);
-    h->xplan_state = -1;
-    return code;
-  };
-  if ((rc = pfd_dmalloc((void **)&p->lh, (size_t)n + 64)) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->kids, (size_t)n + 64)) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->tord, ntiles * XTC * sizeof(uint16_t))) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->toff, ntiles * XOFF * sizeof(uint16_t))) != PFD_OK) return fail(rc);
-  k_plan_tile<<<dim3(ntc, ntr), 256, 0, h->stream>>>(h->ncode, (u32)h->nrow, (u32)h->ncol, ntc, p->lh, p->kids, p->tord,
-                                                     p->toff, block ? h->halo_raw : nullptr, (u32)h->halo_top,
-                                                     (u32)(h->halo_top + h->own_rows - 1));
-  XDBG(h, "k_plan_tile");
-  xdigest(h, "upa", upa.p, (size_t)n * 4);
-  xdigest(h, "ncode", h->ncode, (size_t)n);
-  xdigest(h, "lh", p->lh, (size_t)n);
-  xdigest(h, "kids", p->kids, (size_t)n);
-  xdigest(h, "toff", p->toff, ntiles * XOFF * 2);
-  if (hipGetLastError() != hipSuccess) return fail(PFD_EHIP);
-  DevBuf hcode, tidxbuf, hinfo, hops, tailnum;
-  if ((rc = hcode.alloc((size_t)n + 64)) != PFD_OK) return fail(rc);
-  if ((rc = tidxbuf.alloc((size_t)n * sizeof(u32) + 64)) != PFD_OK) return fail(rc);  // (written at the chain ends only)
-  if ((rc = hinfo.alloc((size_t)n * sizeof(uint16_t) + 64)) != PFD_OK) return fail(rc);
-  DevBuf bcount;
-  const u32 gridT = (u32)ntiles;  // (the chain-end count / list kernels: a 64 x 64 tile per workgroup)
-  if ((rc = bcount.alloc(((size_t)gridT + 1) * sizeof(u32))) != PFD_OK) return fail(rc);
-  if (hipMemsetAsync(bcount.as<u32>() + gridT, 0, sizeof(u32), h->stream) != hipSuccess) return fail(PFD_EHIP);
-  k_plan_heavy_tile<<<dim3(ntc, ntr), 256, 0, h->stream>>>(h->ncode, (u32)h->nrow, (u32)h->ncol, p->lh, p->kids, upa.as<u32>(),
-                                                           hinfo.as<uint16_t>(), hcode.as<u8>());
-  k_plan_count_ends<<<gridT, 256, 0, h->stream>>>(hcode.as<u8>(), n, (u32)h->nrow, (u32)h->ncol, ntc, bcount.as<u32>());
-  XDBG(h, "k_plan_heavy");
-  xdigest(h, "hcode", hcode.p, (size_t)n);
-  xdigest(h, "hinfo", hinfo.p, (size_t)n * 2);
-  if (hipGetLastError() != hipSuccess) return fail(PFD_EHIP);
-  if ((rc = hops.alloc((size_t)n * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = tailnum.alloc((size_t)n * sizeof(u32))) != PFD_OK) return fail(rc);
-  // hops to the end of the chain and the end itself (its index + 1), one path query for both
-  if ((rc = pfd_path_rank_tails(h, hcode.as<u8>(), hops.as<u32>(), tailnum.as<u32>(), &complete)) != PFD_OK) return fail(rc);
-  if (!complete) return fail(PFD_OK);
-  xdigest(h, "hops", hops.p, (size_t)n * 4);
-  xdigest(h, "tailnum", tailnum.p, (size_t)n * 4);
+
+  // leaf steps per tile, heavy links, chain ends per tile; hops to and number of the chain end of every trunk cell
+  int heavy_forest(int *complete) {
+    p = new ExactPlan();
+    h->xplan = p;  // (released by pfd_free_xplan also when a later step fails)
+    p->ntr = ntr, p->ntc = ntc;
+    PFDCHK(p->lh.alloc(h, (size_t)n + 64));
+    PFDCHK(p->kids.alloc(h, (size_t)n + 64));
+    PFDCHK(p->tord.alloc(h, ntiles * XTC * sizeof(uint16_t)));
+    PFDCHK(p->toff.alloc(h, ntiles * XOFF * sizeof(uint16_t)));
+    k_plan_tile<<<dim3(ntc, ntr), 256, 0, h->stream>>>(h->ncode, (u32)h->nrow, (u32)h->ncol, ntc, p->lh, p->kids, p->tord,
+                                                       p->toff, block ? h->halo_raw : nullptr, (u32)h->halo_top,
+                                                       (u32)(h->halo_top + h->own_rows - 1));
+    XDBG(h, "k_plan_tile");
+    xdigest(h, "upa", upa.p, (size_t)n * 4);
+    xdigest(h, "ncode", h->ncode, (size_t)n);
+    xdigest(h, "lh", p->lh, (size_t)n);
+    xdigest(h, "kids", p->kids, (size_t)n);
+    xdigest(h, "toff", p->toff, ntiles * XOFF * 2);
+    KCHK();
+    PFDCHK(hcode.alloc((size_t)n + 64));
+    PFDCHK(tidx_at.alloc((size_t)n * sizeof(u32) + 64));  // (written at the chain ends only)
+    PFDCHK(hinfo.alloc((size_t)n * sizeof(uint16_t) + 64));
+    PFDCHK(bcount.alloc((ntiles + 1) * sizeof(u32)));
+    HIPCHK(hipMemsetAsync(bcount + ntiles, 0, sizeof(u32), h->stream));
+    k_plan_heavy_tile<<<dim3(ntc, ntr), 256, 0, h->stream>>>(h->ncode, (u32)h->nrow, (u32)h->ncol, p->lh, p->kids, upa, hinfo, hcode);
+    k_plan_count_ends<<<(u32)ntiles, 256, 0, h->stream>>>(hcode, n, (u32)h->nrow, (u32)h->ncol, ntc, bcount);
+    XDBG(h, "k_plan_heavy");
+    xdigest(h, "hcode", hcode.p, (size_t)n);
+    xdigest(h, "hinfo", hinfo.p, (size_t)n * 2);
+    KCHK();
+    PFDCHK(allocs((size_t)n * sizeof(u32), hops, tailnum));
+    // hops to the end of the chain and the end itself (its index + 1), one path query for both
+    PFDCHK(pfd_path_rank_tails(h, hcode, hops, tailnum, complete));
+    if (!*complete) return PFD_OK;
+    xdigest(h, "hops", hops.p, (size_t)n * 4);
+    xdigest(h, "tailnum", tailnum.p, (size_t)n * 4);
+    return PFD_OK;
+  }
+
   // the chain ends (pits of the heavy forest), in raster order (selection by scan: no same-address atomics).  The list
   // lives in the upstream-area buffer, which is no longer needed.
-  DevBuf dA, dB, pA, pB, tmp, cnt, len_of, rank_of, parb;
-  u32 *tails = upa.as<u32>();
-  if ((rc = cnt.alloc(64 * sizeof(u32))) != PFD_OK) return fail(rc);
-  size_t tmp_bytes = 0;
-  {
-    if (rocprim::exclusive_scan(nullptr, tmp_bytes, bcount.as<u32>(), bcount.as<u32>(), 0u, (size_t)gridT + 1, rocprim::plus<u32>(),
-                                h->stream) != hipSuccess)
-      return fail(PFD_EHIP);
-    if ((rc = tmp.alloc(std::max<size_t>(tmp_bytes, 16))) != PFD_OK) return fail(rc);
-    if (rocprim::exclusive_scan(tmp.p, tmp_bytes, bcount.as<u32>(), bcount.as<u32>(), 0u, (size_t)gridT + 1, rocprim::plus<u32>(),
-                                h->stream) != hipSuccess)
-      return fail(PFD_EHIP);
-    k_plan_tail_list<<<gridT, 256, 0, h->stream>>>(hcode.as<u8>(), n, (u32)h->nrow, (u32)h->ncol, ntc, bcount.as<u32>(), tails);
-    if (hipGetLastError() != hipSuccess) return fail(PFD_EHIP);
+  int chain_ends() {
+    tails = upa;
+    PFDCHK(cnt.alloc(64 * sizeof(u32)));
+    PFDCHK(scan(bcount.as<u32>(), bcount.as<u32>(), ntiles + 1));
+    k_plan_tail_list<<<(u32)ntiles, 256, 0, h->stream>>>(hcode, n, (u32)h->nrow, (u32)h->ncol, ntc, bcount, tails);
+    KCHK();
+    hcode.alloc(0);
+    HIPCHK(hipMemcpyAsync(&nt32, bcount + ntiles, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    nchain = nt32;
+    nc1 = std::max<size_t>(nchain, 1);
+    if (nchain) k_plan_tidx<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(tails, nt32, tidx_at);
+    XDBG(h, "k_plan_tidx");
+    return PFD_OK;
   }
-  hcode.alloc(0);
-  u32 nt32 = 0;
-  if (hipMemcpyAsync(&nt32, bcount.as<u32>() + gridT, sizeof(u32), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  const unsigned long long nchain = nt32;
-  const size_t nc1 = std::max<size_t>(nchain, 1);
-  u32 *tidx_at = tidxbuf.as<u32>();
-  if (nchain) k_plan_tidx<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(tails, nt32, tidx_at);
-  XDBG(h, "k_plan_tidx");
-  // rounds of the chains (see k_plan_tails)
-  if ((rc = dA.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = dB.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = pA.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = pB.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = parb.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  u32 *Dc = dA.as<u32>(), *Dn = dB.as<u32>(), *Pc = pA.as<u32>(), *Pn = pB.as<u32>();
-  if (nchain) {
-    k_plan_tails<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(h->ncode, h->geo, tails, nt32, tailnum.as<u32>(), tidx_at, Dc, Pc,
-                                                               parb.as<u32>());
-  XDBG(h, "k_plan_tails");
-    for (int r = 0; r < 6; ++r) {
-      k_plan_depth_round<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(nt32, Dc, Pc, Dn, Pn);
-  XDBG(h, "k_plan_depth_round");
-      std::swap(Dc, Dn);
-      std::swap(Pc, Pn);
+
+  // rounds of the chains (see k_plan_tails) and their lengths
+  int rounds() {
+    PFDCHK(allocs(nc1 * sizeof(u32), dA, dB, pA, pB, parb));
+    u32 *Dc = dA, *Dn = dB, *Pc = pA, *Pn = pB;
+    if (nchain) {
+      k_plan_tails<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(h->ncode, h->geo, tails, nt32, tailnum, tidx_at, Dc, Pc, parb);
+      XDBG(h, "k_plan_tails");
+      for (int r = 0; r < 6; ++r) {
+        k_plan_depth_round<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(nt32, Dc, Pc, Dn, Pn);
+        XDBG(h, "k_plan_depth_round");
+        std::swap(Dc, Dn);
+        std::swap(Pc, Pn);
+      }
     }
+    depth = Dc;
+    PFDCHK(allocs(nc1 * sizeof(u32), len_of, rank_of));
+    k_plan_len<<<cdiv_u32(n, 2048), 256, 0, h->stream>>>(hinfo, hops, tailnum, tidx_at, n, len_of);
+    XDBG(h, "k_plan_len");
+    xdigest(h, "tails", tails, (size_t)nchain * 4);
+    xdigest(h, "depth", depth, (size_t)nchain * 4);
+    xdigest(h, "len_of", len_of.p, (size_t)nchain * 4);
+    return PFD_OK;
   }
-  const u32 *depth = Dc;
-  if ((rc = len_of.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = rank_of.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  k_plan_len<<<cdiv_u32(n, 2048), 256, 0, h->stream>>>(hinfo.as<uint16_t>(), hops.as<u32>(), tailnum.as<u32>(), tidx_at, n,
-                                                       len_of.as<u32>());
-  XDBG(h, "k_plan_len");
-  xdigest(h, "tails", tails, (size_t)nchain * 4);
-  xdigest(h, "depth", depth, (size_t)nchain * 4);
-  xdigest(h, "len_of", len_of.p, (size_t)nchain * 4);
-  // chains in layout order: stable sort of the chain ends by round; chain id = rank in that order
-  DevBuf ucell, w, cpos, clenp, ctail, cpad, pick, keys, keys2, iota, cj, adj;
-  if ((rc = keys.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = keys2.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = iota.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = cj.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = adj.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = ctail.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = cpos.alloc((nchain + 1) * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = clenp.alloc(nc1 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = cpad.alloc((nchain + 1) * sizeof(u32))) != PFD_OK) return fail(rc);
-  if (hipMemsetAsync(cnt.p, 0, 64 * sizeof(u32), h->stream) != hipSuccess) return fail(PFD_EHIP);
-  if (nchain) {
-    k_plan_keys<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(nt32, depth, keys.as<u32>(), iota.as<u32>(), cnt.as<u32>());
-  XDBG(h, "k_plan_keys");
-    if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.as<u32>(), keys2.as<u32>(), iota.as<u32>(), cj.as<u32>(),
-                                  (size_t)nchain, 0u, 5u, h->stream) != hipSuccess)
-      return fail(PFD_EHIP);
-    if ((rc = tmp.alloc(std::max<size_t>(tmp_bytes, 16))) != PFD_OK) return fail(rc);
-    if (rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.as<u32>(), keys2.as<u32>(), iota.as<u32>(), cj.as<u32>(),
-                                  (size_t)nchain, 0u, 5u, h->stream) != hipSuccess)
-      return fail(PFD_EHIP);
-  }
-  k_plan_chain_lens<<<cdiv_u32(nchain + 1, 256), 256, 0, h->stream>>>(cj.as<u32>(), nt32, tails, len_of.as<u32>(),
-                                                                     rank_of.as<u32>(), ctail.as<u32>(), clenp.as<u32>(),
-                                                                     cpos.as<u32>(), tidx_at);
-  XDBG(h, "k_plan_chain_lens");
-  xdigest(h, "cj", cj.p, (size_t)nchain * 4);
-  xdigest(h, "ctail", ctail.p, (size_t)nchain * 4);
-  if (rocprim::exclusive_scan(nullptr, tmp_bytes, cpos.as<u32>(), cpos.as<u32>(), 0u, (size_t)nchain + 1,
-                              rocprim::plus<u32>(), h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  if ((rc = tmp.alloc(std::max<size_t>(tmp_bytes, 16))) != PFD_OK) return fail(rc);
-  if (rocprim::exclusive_scan(tmp.p, tmp_bytes, cpos.as<u32>(), cpos.as<u32>(), 0u, (size_t)nchain + 1,
-                              rocprim::plus<u32>(), h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  u32 hist[32], npos32 = 0;
-  if (hipMemcpyAsync(hist, cnt.p, sizeof(hist), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipMemcpyAsync(&npos32, cpos.as<u32>() + nchain, sizeof(u32), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  const unsigned long long npos = npos32;
-  {
+
+  // chains in layout order: stable sort of the chain ends by round; chain id = rank in that order; chains per round
+  int layout() {
+    PFDCHK(allocs(nc1 * sizeof(u32), keys, keys2, iota, cj, adj, ctail));
+    PFDCHK(cpos.alloc((nchain + 1) * sizeof(u32)));
+    PFDCHK(clenp.alloc(nc1 * sizeof(u32)));
+    PFDCHK(cpad.alloc((nchain + 1) * sizeof(u32)));
+    HIPCHK(hipMemsetAsync(cnt.p, 0, 64 * sizeof(u32), h->stream));
+    if (nchain) {
+      k_plan_keys<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(nt32, depth, keys, iota, cnt);
+      XDBG(h, "k_plan_keys");
+      PFDCHK(pfd_rocprim(tmp, [&](void *t, size_t &b) {
+        return rocprim::radix_sort_pairs(t, b, keys.as<u32>(), keys2.as<u32>(), iota.as<u32>(), cj.as<u32>(), (size_t)nchain,
+                                         0u, 5u, h->stream);
+      }));
+    }
+    k_plan_chain_lens<<<cdiv_u32(nchain + 1, 256), 256, 0, h->stream>>>(cj, nt32, tails, len_of, rank_of, ctail, clenp, cpos,
+                                                                       tidx_at);
+    XDBG(h, "k_plan_chain_lens");
+    xdigest(h, "cj", cj.p, (size_t)nchain * 4);
+    xdigest(h, "ctail", ctail.p, (size_t)nchain * 4);
+    PFDCHK(scan(cpos.as<u32>(), cpos.as<u32>(), (size_t)nchain + 1));
+    u32 hist[32], npos32 = 0;
+    HIPCHK(hipMemcpyAsync(hist, cnt.p, sizeof(hist), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&npos32, cpos + nchain, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    npos = npos32;
     i64 c = 0;
     for (int b = 0; b < 32; ++b) {
       p->b_chain[b] = c;
       c += hist[b];
     }
     p->b_chain[32] = c;
+    p->ntrunk = (i64)npos;
+    p->nchain = (i64)nchain;
+    upa.alloc(0);  // (the list of chain ends is no longer needed: ctail holds them in layout order)
+    return PFD_OK;
   }
-  p->ntrunk = (i64)npos;
-  p->nchain = (i64)nchain;
-  upa.alloc(0);  // (the list of chain ends is no longer needed: ctail holds them in layout order)
-  if ((rc = ucell.alloc((npos + 1) * sizeof(uint4))) != PFD_OK) return fail(rc);
-  if ((rc = w.alloc((npos + 1) * sizeof(u32))) != PFD_OK) return fail(rc);
-  if (hipMemsetAsync(ucell.p, 0, (npos + 1) * sizeof(uint4), h->stream) != hipSuccess) return fail(PFD_EHIP);
-  if ((rc = pfd_dmalloc((void **)&p->cslot, ((size_t)n + 64) * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->tl_off, (ntiles + 1) * sizeof(u32))) != PFD_OK) return fail(rc);
-  if (hipMemsetAsync(p->tl_off + ntiles, 0, sizeof(u32), h->stream) != hipSuccess) return fail(PFD_EHIP);
-  DevBuf pend;  // (written at the chain ends only, like tidx_at)
-  if ((rc = pend.alloc((size_t)n * sizeof(u32) + 64)) != PFD_OK) return fail(rc);
-  if (nchain)
-    k_plan_pend<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(ctail.as<u32>(), cpos.as<u32>(), clenp.as<u32>(), nt32, pend.as<u32>());
-  k_plan_scatter<<<dim3(ntc, ntr), 256, 0, h->stream>>>(hinfo.as<uint16_t>(), hops.as<u32>(), tailnum.as<u32>(), tidx_at,
-                                                        pend.as<u32>(), (u32)h->nrow, (u32)h->ncol,
-                                                        ucell.as<uint4>(), p->cslot, p->tl_off);
-  // first list entry of every tile (exclusive scan of the tiles' trunk counts, in place)
-  if (rocprim::exclusive_scan(nullptr, tmp_bytes, p->tl_off, p->tl_off, 0u, ntiles + 1, rocprim::plus<u32>(), h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  if ((rc = tmp.alloc(std::max<size_t>(tmp_bytes, 16))) != PFD_OK) return fail(rc);
-  if (rocprim::exclusive_scan(tmp.p, tmp_bytes, p->tl_off, p->tl_off, 0u, ntiles + 1, rocprim::plus<u32>(), h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  if ((rc = pfd_dmalloc((void **)&p->tlist, (npos + 1) * sizeof(uint2))) != PFD_OK) return fail(rc);
-  XDBG(h, "k_plan_scatter");
-  if (hipGetLastError() != hipSuccess) return fail(PFD_EHIP);
-  // slot of a position = exclusive scan of the slots the positions before it need (in place)
-  auto wneed = rocprim::make_transform_iterator((const uint4 *)ucell.p, XRecSlots());
-  if (rocprim::exclusive_scan(nullptr, tmp_bytes, wneed, w.as<u32>(), 0u, (size_t)npos + 1, rocprim::plus<u32>(),
-                              h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  if ((rc = tmp.alloc(std::max<size_t>(tmp_bytes, 16))) != PFD_OK) return fail(rc);
-  if (rocprim::exclusive_scan(tmp.p, tmp_bytes, wneed, w.as<u32>(), 0u, (size_t)npos + 1, rocprim::plus<u32>(),
-                              h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  // padded chain starts: exclusive scan of the padded chain lengths; round offsets = starts of their first chains
-  k_plan_chain_len<<<cdiv_u32(nchain + 1, 256), 256, 0, h->stream>>>(cpos.as<u32>(), clenp.as<u32>(), w.as<u32>(),
-                                                                    (u32)nchain, cpad.as<u32>());
-  XDBG(h, "k_plan_chain_len");
-  if (rocprim::exclusive_scan(nullptr, tmp_bytes, cpad.as<u32>(), cpad.as<u32>(), 0u, (size_t)nchain + 1,
-                              rocprim::plus<u32>(), h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  if ((rc = tmp.alloc(std::max<size_t>(tmp_bytes, 16))) != PFD_OK) return fail(rc);
-  if (rocprim::exclusive_scan(tmp.p, tmp_bytes, cpad.as<u32>(), cpad.as<u32>(), 0u, (size_t)nchain + 1,
-                              rocprim::plus<u32>(), h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  u32 pidx[33], pval[33];
-  for (int b = 0; b <= 32; ++b) pidx[b] = (u32)p->b_chain[b];
-  if ((rc = pick.alloc(2 * 33 * sizeof(u32))) != PFD_OK) return fail(rc);
-  if (hipMemcpyAsync(pick.p, pidx, sizeof(pidx), hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(PFD_EHIP);
-  k_plan_pick<<<1, 64, 0, h->stream>>>(cpad.as<u32>(), pick.as<u32>(), 33, pick.as<u32>() + 33);
-  XDBG(h, "k_plan_pick");
-  if (hipMemcpyAsync(pval, pick.as<u32>() + 33, sizeof(pval), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  for (int b = 0; b <= 32; ++b) p->b_slot[b] = (i64)pval[b];
-  p->nslot = (i64)pval[32];
-  const size_t nsl = std::max<size_t>((size_t)p->nslot, 4);
-  const size_t nwords = nsl / 32 + 4;
-  if ((rc = pfd_dmalloc((void **)&p->scell, nsl * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->sinfo, nsl * sizeof(uint16_t) + 16)) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->spost, nwords * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->cstart, std::max<size_t>(nchain, 1) * sizeof(u32))) != PFD_OK) return fail(rc);
-  if ((rc = pfd_dmalloc((void **)&p->clen, std::max<size_t>(nchain, 1) * sizeof(u32))) != PFD_OK) return fail(rc);
-  // padding slots: post slots that carry cell 0 (never folded: they lie beyond their chain's length)
-  if (hipMemsetAsync(p->scell, 0, nsl * sizeof(u32), h->stream) != hipSuccess ||
-      hipMemsetAsync(p->sinfo, 0x80, nsl * sizeof(uint16_t), h->stream) != hipSuccess ||
-      hipMemsetAsync(p->spost, 0, nwords * sizeof(u32), h->stream) != hipSuccess)
-    return fail(PFD_EHIP);
-  if (npos) {
-    k_plan_chains<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(cpos.as<u32>(), clenp.as<u32>(), ctail.as<u32>(),
-                                                                w.as<u32>(), cpad.as<u32>(), hinfo.as<uint16_t>(),
-                                                                (u32)nchain, p->cstart, p->clen, adj.as<u32>());
-  XDBG(h, "k_plan_chains");
-    k_plan_expand<<<cdiv_u32(npos, 256), 256, 0, h->stream>>>(ucell.as<uint4>(), w.as<u32>(), adj.as<u32>(), h->geo, (u32)npos,
-                                                              p->scell, p->sinfo, p->spost);
-  XDBG(h, "k_plan_expand");
-    k_plan_cslot<<<dim3(ntc, ntr), 256, 0, h->stream>>>(hinfo.as<uint16_t>(), w.as<u32>(), (u32)h->nrow,
-                                                        (u32)h->ncol, p->cslot, p->lh, p->tl_off, p->tlist);
-  XDBG(h, "k_plan_cslot");
-  xdigest(h, "ucell", ucell.p, (size_t)npos * 16);
-  xdigest(h, "scell", p->scell, (size_t)p->nslot * 4);
-  xdigest(h, "sinfo", p->sinfo, (size_t)p->nslot * 2);
-  xdigest(h, "spost", p->spost, (size_t)(p->nslot / 32) * 4);
-  xdigest(h, "cstart", p->cstart, (size_t)nchain * 4);
-  xdigest(h, "clen", p->clen, (size_t)nchain * 4);
+
+  // position of every trunk cell (chain order, unpadded), one record per position; the tiles' dense lists of trunk cells
+  int positions() {
+    PFDCHK(ucell.alloc((npos + 1) * sizeof(uint4)));
+    PFDCHK(w.alloc((npos + 1) * sizeof(u32)));
+    HIPCHK(hipMemsetAsync(ucell.p, 0, (npos + 1) * sizeof(uint4), h->stream));
+    PFDCHK(p->cslot.alloc(h, ((size_t)n + 64) * sizeof(u32)));
+    PFDCHK(p->tl_off.alloc(h, (ntiles + 1) * sizeof(u32)));
+    HIPCHK(hipMemsetAsync(p->tl_off + ntiles, 0, sizeof(u32), h->stream));
+    PFDCHK(pend.alloc((size_t)n * sizeof(u32) + 64));  // (written at the chain ends only, like tidx_at)
+    if (nchain) k_plan_pend<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(ctail, cpos, clenp, nt32, pend);
+    k_plan_scatter<<<dim3(ntc, ntr), 256, 0, h->stream>>>(hinfo, hops, tailnum, tidx_at, pend, (u32)h->nrow, (u32)h->ncol, ucell,
+                                                          p->cslot, p->tl_off);
+    // first list entry of every tile (exclusive scan of the tiles' trunk counts, in place)
+    PFDCHK(scan(p->tl_off.p, p->tl_off.p, ntiles + 1));
+    PFDCHK(p->tlist.alloc(h, (npos + 1) * sizeof(uint2)));
+    XDBG(h, "k_plan_scatter");
+    KCHK();
+    return PFD_OK;
   }
+
+  // slots: a position's slot, the chains' padded starts, the rounds' offsets, then the slot arrays themselves
+  int slots() {
+    // slot of a position = exclusive scan of the slots the positions before it need
+    PFDCHK(scan(rocprim::make_transform_iterator((const uint4 *)ucell.p, XRecSlots()), w.as<u32>(), (size_t)npos + 1));
+    // padded chain starts: exclusive scan of the padded chain lengths; round offsets = starts of their first chains
+    k_plan_chain_len<<<cdiv_u32(nchain + 1, 256), 256, 0, h->stream>>>(cpos, clenp, w, (u32)nchain, cpad);
+    XDBG(h, "k_plan_chain_len");
+    PFDCHK(scan(cpad.as<u32>(), cpad.as<u32>(), (size_t)nchain + 1));
+    u32 pidx[33], pval[33];
+    for (int b = 0; b <= 32; ++b) pidx[b] = (u32)p->b_chain[b];
+    PFDCHK(pick.alloc(2 * 33 * sizeof(u32)));
+    HIPCHK(hipMemcpyAsync(pick.p, pidx, sizeof(pidx), hipMemcpyHostToDevice, h->stream));
+    k_plan_pick<<<1, 64, 0, h->stream>>>(cpad, pick, 33, pick + 33);
+    XDBG(h, "k_plan_pick");
+    HIPCHK(hipMemcpyAsync(pval, pick + 33, sizeof(pval), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int b = 0; b <= 32; ++b) p->b_slot[b] = (i64)pval[b];
+    p->nslot = (i64)pval[32];
+    const size_t nsl = std::max<size_t>((size_t)p->nslot, 4);
+    const size_t nwords = nsl / 32 + 4;
+    PFDCHK(p->scell.alloc(h, nsl * sizeof(u32)));
+    PFDCHK(p->sinfo.alloc(h, nsl * sizeof(uint16_t) + 16));
+    PFDCHK(p->spost.alloc(h, nwords * sizeof(u32)));
+    PFDCHK(p->cstart.alloc(h, nc1 * sizeof(u32)));
+    PFDCHK(p->clen.alloc(h, nc1 * sizeof(u32)));
+    // padding slots: post slots that carry cell 0 (never folded: they lie beyond their chain's length)
+    HIPCHK(hipMemsetAsync(p->scell, 0, nsl * sizeof(u32), h->stream));
+    HIPCHK(hipMemsetAsync(p->sinfo, 0x80, nsl * sizeof(uint16_t), h->stream));
+    HIPCHK(hipMemsetAsync(p->spost, 0, nwords * sizeof(u32), h->stream));
+    if (!npos) return PFD_OK;
+    k_plan_chains<<<cdiv_u32(nchain, 256), 256, 0, h->stream>>>(cpos, clenp, ctail, w, cpad, hinfo, (u32)nchain, p->cstart,
+                                                                p->clen, adj);
+    XDBG(h, "k_plan_chains");
+    k_plan_expand<<<cdiv_u32(npos, 256), 256, 0, h->stream>>>(ucell, w, adj, h->geo, (u32)npos, p->scell, p->sinfo,
+                                                              p->spost);
+    XDBG(h, "k_plan_expand");
+    k_plan_cslot<<<dim3(ntc, ntr), 256, 0, h->stream>>>(hinfo, w, (u32)h->nrow, (u32)h->ncol, p->cslot, p->lh, p->tl_off,
+                                                        p->tlist);
+    XDBG(h, "k_plan_cslot");
+    xdigest(h, "ucell", ucell.p, (size_t)npos * 16);
+    xdigest(h, "scell", p->scell, (size_t)p->nslot * 4);
+    xdigest(h, "sinfo", p->sinfo, (size_t)p->nslot * 2);
+    xdigest(h, "spost", p->spost, (size_t)(p->nslot / 32) * 4);
+    xdigest(h, "cstart", p->cstart, (size_t)nchain * 4);
+    xdigest(h, "clen", p->clen, (size_t)nchain * 4);
+    return PFD_OK;
+  }
+
   // the long chains (one wave each in the sweeps): their ids in layout order, offsets per round
-  if (nchain) {
-    const size_t cap = (size_t)p->nslot / XLONG + 1;
-    if ((rc = pfd_dmalloc((void **)&p->longc, cap * sizeof(u32))) != PFD_OK) return fail(rc);
-    rocprim::counting_iterator<u32> ids(0u);
-    auto flags = rocprim::make_transform_iterator(p->clen, [] __device__(u32 cl) { return (cl & XC_LEN) >= XLONG; });
-    if (rocprim::select(nullptr, tmp_bytes, ids, flags, p->longc, cnt.as<u32>(), (size_t)nchain, h->stream) != hipSuccess)
-      return fail(PFD_EHIP);
-    if ((rc = tmp.alloc(std::max<size_t>(tmp_bytes, 16))) != PFD_OK) return fail(rc);
-    if (rocprim::select(tmp.p, tmp_bytes, ids, flags, p->longc, cnt.as<u32>(), (size_t)nchain, h->stream) != hipSuccess)
-      return fail(PFD_EHIP);
+  int long_chains() {
+    if (!nchain) return PFD_OK;
+    PFDCHK(p->longc.alloc(h, ((size_t)p->nslot / XLONG + 1) * sizeof(u32)));
+    PFDCHK(pfd_rocprim(tmp, [&](void *t, size_t &b) {
+      return rocprim::select(t, b, rocprim::counting_iterator<u32>(0u), rocprim::make_transform_iterator(p->clen.p, XIsLong()),
+                             p->longc.p, cnt.as<u32>(), (size_t)nchain, h->stream);
+    }));
     u32 nl = 0;
-    if (hipMemcpyAsync(&nl, cnt.p, sizeof(u32), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
-      return fail(PFD_EHIP);
+    HIPCHK(hipMemcpyAsync(&nl, cnt.p, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     p->nlong = nl;
     std::vector<u32> lc(nl);
-    if (nl && hipMemcpy(lc.data(), p->longc, (size_t)nl * sizeof(u32), hipMemcpyDeviceToHost) != hipSuccess) return fail(PFD_EHIP);
+    if (nl) HIPCHK(hipMemcpy(lc.data(), p->longc, (size_t)nl * sizeof(u32), hipMemcpyDeviceToHost));
     for (int b = 0; b <= 32; ++b)
       p->b_long[b] = (i64)(std::lower_bound(lc.begin(), lc.end(), (u32)std::min<i64>(p->b_chain[b], 0xFFFFFFFFll)) - lc.begin());
+    if (!nl) return PFD_OK;
     // the longest chain of every round (what a round costs when it is latency: see run_exact_up / run_exact_down)
-    if (nl) {
-      DevBuf ll;
-      if ((rc = ll.alloc((size_t)nl * sizeof(u32))) != PFD_OK) return fail(rc);
-      k_plan_long_lens<<<cdiv_u32(nl, 256), 256, 0, h->stream>>>(p->longc, nl, p->clen, ll.as<u32>());
-      std::vector<u32> lens(nl);
-      if (hipMemcpyAsync(lens.data(), ll.p, (size_t)nl * sizeof(u32), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-          hipStreamSynchronize(h->stream) != hipSuccess)
-        return fail(PFD_EHIP);
-      for (int b = 0; b < 32; ++b)
-        for (i64 i = p->b_long[b]; i < p->b_long[b + 1]; ++i) p->b_maxlen[b] = std::max(p->b_maxlen[b], lens[(size_t)i]);
-    }
+    Scratch<u32> ll;
+    PFDCHK(ll.alloc((size_t)nl * sizeof(u32)));
+    k_plan_long_lens<<<cdiv_u32(nl, 256), 256, 0, h->stream>>>(p->longc, nl, p->clen, ll);
+    std::vector<u32> lens(nl);
+    HIPCHK(hipMemcpyAsync(lens.data(), ll.p, (size_t)nl * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int b = 0; b < 32; ++b)
+      for (i64 i = p->b_long[b]; i < p->b_long[b + 1]; ++i) p->b_maxlen[b] = std::max(p->b_maxlen[b], lens[(size_t)i]);
+    return PFD_OK;
   }
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return fail(PFD_EHIP);
-  p->bytes = 6 * ((size_t)n + 64) + ntiles * (XTC + XOFF) * sizeof(uint16_t) + (size_t)p->nslot * 6 + (size_t)p->nslot / 8 + (size_t)nchain * 8 + (size_t)npos * 8 + ntiles * 4;
-  h->bytes_held += p->bytes;
-  h->xplan_state = 1;
+
+  // PFD_OK with h->xplan_state == 1: the plan is ready; PFD_OK without: this raster gets none (cycles, or a heavy forest
+  // whose path query does not complete); anything else: the error of the step that failed
+  int run() {
+    int complete = 0;
+    PFDCHK(weights(&complete));
+    if (!complete) return PFD_OK;
+    PFDCHK(heavy_forest(&complete));
+    if (!complete) return PFD_OK;
+    PFDCHK(chain_ends());
+    PFDCHK(rounds());
+    PFDCHK(layout());
+    PFDCHK(positions());
+    PFDCHK(slots());
+    PFDCHK(long_chains());
+    KCHK();
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->xplan_state = 1;
+    return PFD_OK;
+  }
+};
+
+// whether the handle may have a plan at all; otherwise its sweeps stay with the level engine
+static bool xplan_eligible(const pfd_raster *h) {
+  if (h->gen) return false;
+  if (h->n > 4294967294ll || pfd_knob("PFD_EXACT_LEVELS")) return false;
+  // (row blocks: the cells of the halo rows hold given values, see k_plan_tile; the codes of the halo rows as given
+  //  must still be around)
+  if ((h->halo_top || h->halo_bot) && (!h->halo_raw || pfd_knob("PFD_BLOCK_LEVELS"))) return false;
+  if (h->acyclic < 0) return false;
+  return cdiv_u32((u64)h->nrow, XT) <= 65535u;  // (tile rows are a grid's y dimension)
+}
+
+int pfd_ensure_xplan(pfd_raster *h, bool allow_block) {
+  if ((h->halo_top || h->halo_bot) && !allow_block) return pfd_require_whole(h, "the exact-order plan");
+  if (h->xplan_state != 0) return PFD_OK;
+  h->xplan_state = -1;
+  if (!xplan_eligible(h)) return PFD_OK;
+  pfd_seg_begin(h, "exact_plan");
+  XplanBuild b(h);
+  const int rc = b.run();
+  if (h->xplan_state != 1) {
+    // the one way out without a plan, whatever the reason: nothing may still write what is released here and when `b`
+    // goes; the segment is closed; the status passes through (PFD_OK: not available, the sweeps take the level engine)
+    (void)hipStreamSynchronize(h->stream);
+    pfd_free_xplan(h);
+    h->xplan_state = -1;
+    pfd_seg_end(h, 0);
+    return rc;
+  }
   pfd_seg_end(h, 14);
 #ifdef PFD_DEVTOOLS
+  const ExactPlan *p = b.p;
   if (getenv("PFD_DEBUG"))
     fprintf(stderr, "[xplan] %lld cells: %lld trunk (%.1f%%) in %lld chains, %lld slots\n", (long long)h->n_valid,
             (long long)p->ntrunk, 100.0 * (double)p->ntrunk / (double)std::max<i64>(h->n_valid, 1), (long long)p->nchain,

@@ -701,15 +701,15 @@ static inline bool xinc_applies(pfd_raster *h, const void *out_dev, size_t tag) 
   return h->block_update == 2 && h->xplan_state == 1 && p && p->xinc_ready && p->inc_valid && p->inc_tag == tag && p->inc_out == out_dev;
 }
 template <class Op>
-static int run_exact_up_inc(pfd_raster *h, const Op &op) {
+static int run_exact_up_inc(pfd_raster *h, const Op &op, const XSeeds &seeds) {
   typedef typename Op::Elem Elem;
   typedef typename Op::V V;
   ExactPlan *p = (ExactPlan *)h->xplan;
   pfd_seg_begin(h, "exact_up_block_update");
-  PFDCHK(pfd_xinc_mark(h, h->xseed, h->xseed_elem));
+  PFDCHK(pfd_xinc_mark(h, seeds.dev, seeds.elem));
   i64 launches = 2;
-  Elem *E = (Elem *)p->incE;
-  V *R = (V *)p->incR;
+  Elem *E = (Elem *)p->incE.p;
+  V *R = (V *)p->incR.p;
   for (int b = 0; b < 32; ++b) {
     const u32 s0 = (u32)p->b_slot[b], s1 = (u32)p->b_slot[b + 1];
     const u32 c0 = (u32)p->b_chain[b], c1 = (u32)p->b_chain[b + 1];
@@ -730,18 +730,19 @@ static int run_exact_up_inc(pfd_raster *h, const Op &op) {
   return PFD_OK;
 }
 
+// seeds: the halo seeds of a row block's sweep (none: a whole raster)
 // keep: 0 = a sweep that leaves nothing behind; 1 = row block: keep the element / value arrays for updates;
 // 2 = row block: `out` holds the result of the kept sweep for other halo seeds — fold only what the changed seeds reach
 // (a full sweep, kept, when there is nothing to update from)
 template <class Op>
-static int run_exact_up(pfd_raster *h, const Op &op, const char *name, int keep = 0) {
+static int run_exact_up(pfd_raster *h, const Op &op, const char *name, const XSeeds &seeds = XSeeds(), int keep = 0) {
   typedef typename Op::Elem Elem;
   typedef typename Op::V V;
   ExactPlan *p = (ExactPlan *)h->xplan;
   const size_t tag = typeid(Op).hash_code();
-  if (!(h->xseed && h->xseed_out && h->halo_raw)) keep = 0;
+  if (!(seeds && h->halo_raw)) keep = 0;
   // (the caller has put the seeds into the halo rows of `out`)
-  if (keep == 2 && xinc_applies(h, h->xseed_out, tag)) return run_exact_up_inc(h, op);
+  if (keep == 2 && xinc_applies(h, seeds.out, tag)) return run_exact_up_inc(h, op, seeds);
   pfd_xinc_drop(h);
   if (keep && pfd_xinc_prepare(h) != PFD_OK) keep = 0;
   pfd_seg_begin(h, name);
@@ -750,32 +751,30 @@ static int run_exact_up(pfd_raster *h, const Op &op, const char *name, int keep 
   k_xtile_up<Op><<<dim3(p->ntc, p->ntr), 256, 0, h->stream>>>(op, a);
   KCHK();
   XDBG(h, "tile_up");
-  if (h->xseed && h->xseed_out) {  // row block: the tile pass wrote the halo cells like any other; their values are given
-    const size_t rowb = (size_t)h->ncol * h->xseed_elem;
+  if (seeds) {  // row block: the tile pass wrote the halo cells like any other; their values are given
+    const size_t rowb = (size_t)h->ncol * seeds.elem;
     if (h->halo_top)
-      HIPCHK(hipMemcpyAsync((char *)h->xseed_out + (size_t)(h->halo_top - 1) * rowb, h->xseed, rowb, hipMemcpyDeviceToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync((char *)seeds.out + (size_t)(h->halo_top - 1) * rowb, seeds.dev, rowb, hipMemcpyDeviceToDevice, h->stream));
     if (h->halo_bot)
-      HIPCHK(hipMemcpyAsync((char *)h->xseed_out + (size_t)(h->halo_top + h->own_rows) * rowb, (const char *)h->xseed + rowb, rowb,
+      HIPCHK(hipMemcpyAsync((char *)seeds.out + (size_t)(h->halo_top + h->own_rows) * rowb, (const char *)seeds.dev + rowb, rowb,
                             hipMemcpyDeviceToDevice, h->stream));
   }
   DevBuf Eb, Rb;
   const size_t ebytes = std::max<size_t>((size_t)p->nslot, 1) * sizeof(Elem) + 64, rbytes = std::max<size_t>((size_t)p->nslot, 1) * sizeof(V) + 64;
-  const size_t sbytes = 2 * (size_t)h->ncol * h->xseed_elem;
+  const size_t sbytes = 2 * (size_t)h->ncol * seeds.elem;
   if (keep) {
     int rc;
-    if ((rc = pfd_dmalloc(&p->incE, ebytes)) != PFD_OK || (rc = pfd_dmalloc(&p->incR, rbytes)) != PFD_OK ||
-        (rc = pfd_dmalloc(&p->incSeed, sbytes)) != PFD_OK) {
+    if ((rc = p->incE.alloc(h, ebytes)) != PFD_OK || (rc = p->incR.alloc(h, rbytes)) != PFD_OK ||
+        (rc = p->incSeed.alloc(h, sbytes)) != PFD_OK) {
       pfd_xinc_drop(h);
       return rc;
     }
-    p->inc_bytes = ebytes + rbytes + sbytes;
-    h->bytes_held += p->inc_bytes;
   } else {
     PFDCHK(Eb.alloc(ebytes));
     PFDCHK(Rb.alloc(rbytes));
   }
-  Elem *E = keep ? (Elem *)p->incE : Eb.as<Elem>();
-  V *R = keep ? (V *)p->incR : Rb.as<V>();
+  Elem *E = keep ? (Elem *)p->incE.p : Eb.as<Elem>();
+  V *R = keep ? (V *)p->incR.p : Rb.as<V>();
   // The last two rounds hold the main stems and their largest tributaries: a few thousand chains, the longest as long
   // as the longest flow path, folded serially — 0.5 ms each at 30000 x 30000 with most of the chip idle.  The tile-order
   // pass that writes the trunk cells (k_xtrunk_unscatter_list, bandwidth) therefore starts BESIDE them, on the handle's
@@ -842,8 +841,8 @@ static int run_exact_up(pfd_raster *h, const Op &op, const char *name, int keep 
   KCHK();
   pfd_seg_end(h, launches);
   if (keep) {  // what an update starts from: this sweep's arrays, seeds and result buffer
-    HIPCHK(hipMemcpyAsync(p->incSeed, h->xseed, sbytes, hipMemcpyDeviceToDevice, h->stream));
-    p->inc_valid = true, p->inc_tag = tag, p->inc_out = h->xseed_out;
+    HIPCHK(hipMemcpyAsync(p->incSeed, seeds.dev, sbytes, hipMemcpyDeviceToDevice, h->stream));
+    p->inc_valid = true, p->inc_tag = tag, p->inc_out = seeds.out;
   }
   HIPCHK(hipStreamSynchronize(h->stream));  // E / R are released on return (unless kept)
   return PFD_OK;

@@ -1,6 +1,6 @@
 // lists.h — the frame the list-producing calls stand on (outlets.hip, streams.hip, basins_ext.hip, subbasins_area.hip,
 // window.hip: path, subgrid.hip; walks.h holds the rocprim-free part): the argument check of a call that returns a list, the
-// handle's links and sequence on the device (pfd_with_graph, pfd_with_links), the scratch of a rocprim call (pfd_rocprim),
+// handle's links and sequence on the device (pfd_with_graph, pfd_with_links),
 // the stable compaction by a mark, the small list kernels, the hand-over of a list to the caller and the tail of a call
 // that returns ragged lists (pfd_ragged_tail).
 #pragma once
@@ -88,24 +88,6 @@ static inline int read_count(pfd_raster *h, const unsigned long long *dev, u64 *
   HIPCHK(hipMemcpyAsync(&v, dev, sizeof(v), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   *out = (u64)v;
-  return PFD_OK;
-}
-
-// The scratch of a rocprim call.  call(p, bytes) -> hipError_t is the rocprim call with its first two arguments left open:
-// asked for its size with p == nullptr, then run in `tmp`.  The caller owns `tmp`, and with it the moment the scratch is
-// released (pfd_dfree waits for the stream).  pfd_rocprim_scratch stops after the allocation: for a call that runs several
-// times in one scratch (the piecewise sort of subgrid.hip).
-template <class Call>
-static int pfd_rocprim_scratch(DevBuf &tmp, Call call, size_t *bytes) {
-  *bytes = 0;
-  HIPCHK(call(nullptr, *bytes));
-  return tmp.alloc(std::max<size_t>(*bytes, 16));
-}
-template <class Call>
-static int pfd_rocprim(DevBuf &tmp, Call call) {
-  size_t bytes = 0;
-  PFDCHK(pfd_rocprim_scratch(tmp, call, &bytes));
-  HIPCHK(call(tmp.p, bytes));
   return PFD_OK;
 }
 

@@ -947,13 +947,10 @@ int pfd_order_cells_by_rank(pfd_raster *h, int *ok) {
   const u32 inval = maxrank + 1;
   auto keys_in = rocprim::make_transform_iterator(keys.as<u32>(), [inval] __device__(u32 k) { return k > inval ? inval : k; });
   rocprim::counting_iterator<u32> cells(0u);
-  size_t tmp_bytes = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_in, keys2.as<u32>(), cells, h->seq, (size_t)n, 0u, (unsigned)bits,
-                                   h->stream));
   DevBuf tmp;
-  PFDCHK(tmp.alloc(tmp_bytes));
-  HIPCHK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys_in, keys2.as<u32>(), cells, h->seq, (size_t)n, 0u, (unsigned)bits,
-                                   h->stream));
+  PFDCHK(pfd_rocprim(tmp, [&](void *t, size_t &b) {
+    return rocprim::radix_sort_pairs(t, b, keys_in, keys2.as<u32>(), cells, h->seq, (size_t)n, 0u, (unsigned)bits, h->stream);
+  }));
   const i64 nlev = (i64)maxrank + 1;
   DevBuf lo;
   PFDCHK(lo.alloc((size_t)(nlev + 1) * sizeof(i64)));

@@ -1813,10 +1813,7 @@ static int up_block_run(const Op &op0, BlockFrame &f, const char *name) {
   } else if (h->xplan_state == 1) {
     // exact-order engine: the tile pass writes every cell, the halo cells among them; their given values go back in
     // before the trunk rounds read them (run_exact_up)
-    h->xseed = seed_dev, h->xseed_out = out_dev, h->xseed_elem = sizeof(T);
-    const int rc = run_exact_up(h, op0, "exact_up_block", h->block_update);
-    h->xseed = nullptr, h->xseed_out = nullptr, h->xseed_elem = 0;
-    PFDCHK(rc);
+    PFDCHK(run_exact_up(h, op0, "exact_up_block", XSeeds{seed_dev, out_dev, sizeof(T)}, h->block_update));
   } else {
     PFDCHK(run_up(h, op, name));
   }

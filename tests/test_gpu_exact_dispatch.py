@@ -147,3 +147,99 @@ def test_row_blocks(gpu_lib, monkeypatch, form, op):
             full[b] += 1
             check_launches(s, info, sweep, sweep == "up" and fuses and form == "suite", f"TAIL_BLOCKS {form} {op} block {b}")
     assert all(full.values()), f"a block never ran {segment}: {full}"
+
+
+def test_plan_bytes_of_a_whole_raster(gpu_lib):
+    """bytes_held grows when the plan is built, by the same amount on every handle of the raster."""
+    from pyflwdir_amd import _hip
+
+    r = X.raster("fuzz_130x67")
+    held = []
+    for _ in range(2):
+        h = _hip.RasterHandle(r.d8, r.shape[0], r.shape[1])
+        before = h.info()["bytes_held"]
+        info = X.xplan_info(h)
+        held.append(h.info()["bytes_held"])
+        h.close()
+        print("fuzz_130x67", info, "bytes_held", before, "->", held[-1])
+        assert info["state"] == 1 and held[-1] > before, (info, before, held)
+    assert held[0] == held[1], held
+
+
+@pytest.mark.parametrize("b", [0, 1])
+def test_kept_block_sweep_bytes_do_not_drift(gpu_lib, b):
+    """fuzz_513x520 in two row blocks: a kept up-sweep (pfd_set_block_update 1) holds at least its element and value
+    arrays — 8 bytes per slot — more than the handle does after pfd_set_block_update(0), a second keep / release cycle
+    ends on the same bytes_held as the first, and both kept sweeps give the plain sweep's bits."""
+    import numpy as np
+
+    from pyflwdir_amd import _hip, dist
+
+    r, nb = X.raster("fuzz_513x520"), 2
+    a, e = dist.block_slice(r.shape[0], nb, b)
+    ncol = r.shape[1]
+    h = dist._block_handle(r.d8, nb, b, [0] * nb)
+    bufs = []
+    try:
+        info = X.xplan_info(h)
+        assert info["state"] == 1 and info["slots"] > 0, info
+        payload = np.ascontiguousarray(r.payloads["f32"].reshape(r.shape)[a:e])
+        data = _hip.DeviceBuffer(payload.nbytes, h.device).upload(payload)
+        out = _hip.DeviceBuffer(payload.nbytes, h.device)
+        bufs += [data, out]
+        seed = np.random.default_rng(513 + b).random(2 * ncol, dtype=np.float32)
+
+        def sweep():
+            h.accuflux_block(data, _hip.PFD_F32, seed, out, nodata_f=X.NODATA["f32"], has_nodata=1, memspace=_hip.PFD_DEVICE)
+            return out.download(np.float32, (e - a, ncol)).tobytes()
+
+        h.set_block_update(0)
+        plain = sweep()
+        released = []
+        for cycle in range(2):
+            h.set_block_update(1)
+            got = sweep()
+            kept = h.info()["bytes_held"]
+            h.set_block_update(0)
+            released.append(h.info()["bytes_held"])
+            print(f"block {b} cycle {cycle}: slots {info['slots']}, bytes_held kept {kept}, released {released[-1]}")
+            assert got == plain, f"block {b} cycle {cycle}: the kept sweep differs from the plain one"
+            assert kept - released[-1] >= 8 * info["slots"], (kept, released, info)
+        assert released[0] == released[1], released
+    finally:
+        for buf in bufs:
+            buf.free()
+        h.close()
+
+
+def test_abandoned_plan_leaves_a_readable_record(gpu_lib):
+    """A raster with cycles gets no plan: the first order-sensitive call records a closed exact_plan segment, then runs on
+    the level engine; the handle remembers (state -1) and the next call does not try again."""
+    import math
+    import os
+
+    import numpy as np
+
+    from pyflwdir_amd import _hip
+
+    d8 = np.ascontiguousarray(np.load(os.path.join(X.GOLD, "synth_loops_96x80.npz"))["d8"], dtype=np.uint8)
+    data = np.random.default_rng(96).random(d8.size, dtype=np.float32)
+    h = _hip.RasterHandle(d8, d8.shape[0], d8.shape[1])
+    try:
+        h.set_profiling(True)
+        first = h.accuflux(data, _hip.PFD_F32, nodata_f=-9999.0)
+        timing = h.last_timing()
+        print("first call", timing)
+        names = [s["name"] for s in timing]
+        assert names.count("exact_plan") == 1 and "sweep_accuflux_up" in names, names
+        plan = timing[names.index("exact_plan")]
+        assert math.isfinite(plan["ms"]) and plan["ms"] >= 0.0, plan
+        assert names.index("sweep_accuflux_up") > names.index("exact_plan"), names
+        assert X.xplan_info(h)["state"] == -1
+        second = h.accuflux(data, _hip.PFD_F32, nodata_f=-9999.0)
+        names = [s["name"] for s in h.last_timing()]
+        print("second call", names)
+        assert "exact_plan" not in names and "sweep_accuflux_up" in names, names
+        assert second.tobytes() == first.tobytes()
+    finally:
+        h.close()
