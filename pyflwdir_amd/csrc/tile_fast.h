@@ -21,7 +21,9 @@
 //  * final pass: a saturated cell points at a per-lane sink word behind the tile's counts, with a pointer word behind
 //    the tile's pointers that points at itself: no compare / select per cell and round;
 //  * one (local) / two (final) barriers per round: the "is any pointer still moving" vote goes through two
-//    alternating LDS flag rows written by the wave leaders instead of three barriers of __syncthreads_or.
+//    alternating LDS flag rows written by the wave leaders instead of three barriers of __syncthreads_or;
+//  * local pass: no barrier at all in the first FX_FREE rounds — its jumps are gather-only and tolerate any
+//    interleaving, so each wave runs them on its own and the voted loop only takes over what is left.
 // The memory phases are the other half, and there the unit is the round trip, not the instruction: the final pass asks
 // for everything its prologue needs — 4 code words, the slot's record, the 5 candidate totals — in ONE batch, nothing
 // waiting in front of the candidates (their addresses come out of registers, fy_cand_row / fy_cand_col), keeps a 16-bit
@@ -38,6 +40,9 @@
 #define FX_PN (TCELLS + PSL + 8)            // P entries of the local pass
 #ifndef FXP
 #define FXP 4  // count words per perimeter slot (replicas picked by lane: a wave's atomics on one word are serialised)
+#endif
+#ifndef FX_FREE
+#define FX_FREE 3  // local pass: jump rounds a wave runs on its own before the voted loop (measured 2..5: DESIGN 4.2)
 #endif
 #define FY_SINK0 (4u * TCELLS)              // final pass: A byte offset of sink word 0 (64 of them, one per lane)
 
@@ -201,6 +206,7 @@ __global__ void __launch_bounds__(256) k_tile_local_fast(TileArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t P[FX_PN];     // byte offset into P of an ancestor / of a root word
   __shared__ __attribute__((aligned(16))) u8 code[HW * CP];
   __shared__ __attribute__((aligned(16))) u32 s_flag[2][4];
+  __shared__ u32 s_free[4];  // profiling level 2: free rounds per wave
   __shared__ u64 s_cnt[4];
   const u32 tid = threadIdx.x;
   u32 bx_, by_;
@@ -331,14 +337,12 @@ __global__ void __launch_bounds__(256) k_tile_local_fast(TileArgs a) {
     pc[4 * j + 3] = pp.y >> 16;
     lv[j] = !(pp.x & pp.y & (pp.x >> 16) & (pp.y >> 16) & FX_SLOT0);  // (offsets < 0x4000: bit 13 <=> root word)
   }
-  int round = 0;
-#pragma nounroll
-  for (; round < MAXROUNDS_TILE; ++round) {
+  auto jump_round = [&]() {
 #pragma unroll
     for (int j = 0; j < QPT; ++j) {
       if (lv[j]) {
-        // two jumps per round (a root word points at itself, so jumping from a root stays there): half the barriers
-        // and pointer write-backs per hop
+        // two jumps per round (a root word points at itself, so jumping from a root stays there): half the
+        // pointer write-backs per hop
         u32 q[4];
 #pragma unroll
         for (int b = 0; b < 4; ++b) q[b] = *(const uint16_t *)((const u8 *)P + pc[4 * j + b]);
@@ -350,11 +354,35 @@ __global__ void __launch_bounds__(256) k_tile_local_fast(TileArgs a) {
         *(uint2 *)&P[4u * tid + 1024u * j] = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
       }
     }
+  };
+  // A jump tolerates reading a pointer its owner has already advanced (every value a pointer ever holds is an
+  // ancestor), so nothing here needs the waves to be in step: the barrier of a round is there for the vote alone.  The
+  // first FX_FREE rounds therefore run per wave, without barrier or vote, while one of the wave's own quads still
+  // moves (a wave that is done has nothing to ask, and the words others read from it are root words).  Free rounds
+  // can be less effective than synchronised ones (a wave may read pointers nobody has advanced yet), never wrong; the
+  // voted loop behind them keeps its full bound, so a path that saturated before still does.  The fence stands where
+  // the barrier stood for the compiler: P is shared, other waves write it between the rounds (it costs the wait for
+  // the round's own write-back, nothing else).  Unrolled on purpose: as a loop the compiler rotates the 16 pointer
+  // registers with copies every round and the pass loses half of what the free rounds gain.
+  int nfree = 0;
+#pragma unroll
+  for (; nfree < FX_FREE; ++nfree) {
+    if (__ballot(lv[0] | lv[1] | lv[2] | lv[3]) == 0ull) break;
+    jump_round();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  }
+  if ((a.flags & 32) && (tid & 63u) == 0u) s_free[tid >> 6] = (u32)nfree;  // (read behind the first vote's barrier)
+  int round = 0;
+#pragma nounroll
+  for (; round < MAXROUNDS_TILE; ++round) {
+    jump_round();
     if (!fx_vote(s_flag, round, tid, lv[0] | lv[1] | lv[2] | lv[3])) break;
   }
   const u32 live = (lv[0] ? 1u : 0u) + (lv[1] ? 1u : 0u) + (lv[2] ? 1u : 0u) + (lv[3] ? 1u : 0u);
   if ((a.flags & 32) && tid == 0) {  // pfd_set_profiling(h, 2): rounds this tile needed (max and sum over the tiles)
-    const unsigned long long r = (unsigned long long)min(round + 1, MAXROUNDS_TILE);
+    // = the free rounds of the wave that was live in most of them + the voted rounds
+    const int rfree = (int)max(max(s_free[0], s_free[1]), max(s_free[2], s_free[3]));
+    const unsigned long long r = (unsigned long long)min(rfree + round + 1, MAXROUNDS_TILE);
     const u32 w = (tr * a.ntc + tc) & 255u;
     atomicMax((unsigned long long *)&a.rcnt[w], r);
     atomicAdd((unsigned long long *)&a.rcnt[256 + w], r);
