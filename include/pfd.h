@@ -46,6 +46,12 @@ extern "C" {
 /* memory spaces */
 #define PFD_HOST 0
 #define PFD_DEVICE 1
+/* Ordering of PFD_DEVICE arguments, the one rule: a call returns only after everything it wrote to the caller's device
+ * buffers is complete in HBM (the sweeps wait for their handle's stream, the elementwise calls and the device helpers
+ * for the null stream), and it reads its device inputs only while it runs.  So a device buffer written by any call of
+ * this library may be passed to any other call — of the same handle, of another handle, or of no handle (pfd_ew_*) —
+ * as soon as the first has returned, and may be freed or overwritten then.  Nothing is left in flight between calls;
+ * a caller that writes such a buffer with its own kernels synchronises them before it passes the buffer in. */
 
 /* element dtype codes (payloads and index exports) */
 #define PFD_I32 1
@@ -81,6 +87,18 @@ int pfd_device_count(int *count);
  * any other GPU library (bench.py uses these). */
 int pfd_malloc(int device, size_t bytes, void **ptr);
 int pfd_free(int device, void *ptr);
+/* pfd_malloc / pfd_free on the library's own caching allocator — a reserved arena first (pfd_reserve), then the cache of
+ * freed blocks by size class, hipMalloc last: blocks for results that come and go with every call (the per-cell arrays of
+ * pyflwdir_amd.DeviceArray), which must not meet hipMalloc / hipFree of multi-GiB blocks in a steady state (0.2 ms or
+ * seconds each; profiles/resident_chain_30000.txt).  The block is rounded up to its size class, is at least 256-byte
+ * aligned and is valid wherever a pfd_malloc block is; it must be released with pfd_free_pooled, which waits until the
+ * device is done with it and hands it to the next taker, the library's working buffers included.  That wait is for the
+ * calling thread's last handle stream (or the whole device when it has none), NOT for the null stream the pfd_ew_* calls
+ * run on: releasing a block those calls wrote is safe only because each of them synchronises before it returns (the
+ * ordering rule above).  A form of the elementwise calls that returned before its kernels finish would have to make this
+ * call wait for the null stream as well. */
+int pfd_malloc_pooled(int device, size_t bytes, void **ptr);
+int pfd_free_pooled(int device, void *ptr);
 int pfd_memcpy_h2d(int device, void *dst_dev, const void *src_host, size_t bytes);
 int pfd_memcpy_d2h(int device, void *dst_host, const void *src_dev, size_t bytes);
 int pfd_device_synchronize(int device);
@@ -740,6 +758,46 @@ int pfd_checksum_i32(int device, const int32_t *dev_ptr, int64_t n, int64_t *sum
 /* number of NaN / +-inf values of a DEVICE array (dtype PFD_F32 or PFD_F64): callers with device-resident elevations check
  * them with it before the row-block HAND (pfd_hand_block), whose "-inf = height not known yet" a non-finite difference imitates */
 int pfd_count_nonfinite(int device, int dtype, const void *dev_ptr, int64_t n, int64_t *count);
+
+/* ---- elementwise: the small expressions between two sweeps, on arrays that stay in HBM (csrc/elementwise.hip) ---------
+ * What a front end computes with numpy between two calls (`drain == 1`, `mask != 0`, `upa > t`, an int -> float64
+ * widening) for per-cell arrays that never leave the device.  No handle: `device` is the GPU, every pointer is a DEVICE
+ * pointer to n elements (n >= 0; n may exceed 2^32), `out` never aliases an input.  Element dtypes: PFD_U8 (also bool:
+ * bytes 0 / 1), PFD_I8, PFD_I32, PFD_U32, PFD_I64, PFD_F32, PFD_F64; any other code is PFD_EUNSUPPORTED.  Scalars travel
+ * as the pair scalar_i (integer dtypes) / scalar_f (float dtypes; rounded to float for PFD_F32), like nodata_i / nodata_f.
+ * Ordering: see "memory spaces" — every call waits for its kernels before it returns.
+ * pfd_ew_compare — out[i] = 1 if the relation holds between a[i] and the scalar, else 0.  `rel` is a set of outcomes, the
+ *   sum of PFD_EW_LT (a < s), PFD_EW_EQ, PFD_EW_GT and PFD_EW_UNORDERED (one side is NaN): < is 1, <= 3, > 4, >= 6, == 2,
+ *   != 13 — IEEE comparisons: NaN gives 0 except for !=, -0.0 == 0.0.  compare_dtype == dtype compares in the array's own
+ *   type; compare_dtype == PFD_F64 converts every element to double first (round to nearest, as a C cast does) and
+ *   compares with scalar_f: what numpy does for an integer or float32 array and a float64 scalar.
+ * pfd_ew_logic — byte masks holding 0 / 1: PFD_EW_AND / PFD_EW_OR / PFD_EW_XOR of a and b, PFD_EW_NOT of a (b ignored).
+ * pfd_ew_where — out[i] = mask[i] != 0 ? a[i] : b[i], or the scalar in place of b[i] when b is NULL; a, b and out of `dtype`.
+ * pfd_ew_convert — the conversions that are exact for every value: PFD_U8 / PFD_I8 -> PFD_I32; PFD_I32 / PFD_U32 ->
+ *   PFD_I64 / PFD_F64; PFD_F32 -> PFD_F64.  Anything else is PFD_EUNSUPPORTED.
+ * pfd_ew_reduce — reductions with one answer whatever the execution order: PFD_EW_COUNT the number of elements != 0 (a NaN
+ *   counts) in *res_i; PFD_EW_MIN / PFD_EW_MAX the smallest / largest element, integer dtypes in *res_i, float dtypes in
+ *   *res_f (as a double; -0.0 orders below 0.0), with *has_nan = 1 when a float array holds a NaN — *res_f is then the
+ *   extreme of the other elements and the caller answers NaN, as np.min / np.max do.  n == 0: PFD_EINVAL for MIN / MAX.
+ *   Two launches (a partial per workgroup, then one workgroup over the partials), no atomics, no float arithmetic. */
+#define PFD_EW_LT 1
+#define PFD_EW_EQ 2
+#define PFD_EW_GT 4
+#define PFD_EW_UNORDERED 8
+#define PFD_EW_AND 0
+#define PFD_EW_OR 1
+#define PFD_EW_XOR 2
+#define PFD_EW_NOT 3
+#define PFD_EW_COUNT 0
+#define PFD_EW_MIN 1
+#define PFD_EW_MAX 2
+int pfd_ew_compare(int device, int rel, int dtype, const void *a, int compare_dtype, int64_t scalar_i, double scalar_f,
+                   uint8_t *out, int64_t n);
+int pfd_ew_logic(int device, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, int64_t n);
+int pfd_ew_where(int device, int dtype, const uint8_t *mask, const void *a, const void *b, int64_t scalar_i, double scalar_f,
+                 void *out, int64_t n);
+int pfd_ew_convert(int device, int src_dtype, const void *a, int dst_dtype, void *out, int64_t n);
+int pfd_ew_reduce(int device, int op, int dtype, const void *a, int64_t n, int64_t *res_i, double *res_f, int *has_nan);
 
 /* ---- synthetic rasters (bench / tests; device twin of oracle/pfd_oracle.c orc_synth_*) ---- */
 /* writes rows [row0, row0+nrows) of the nrow x ncol synthetic raster to device memory */

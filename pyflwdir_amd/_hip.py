@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 
 import numpy as np
 
@@ -25,6 +26,10 @@ PFD_FILL_MAX, PFD_FILL_MIN, PFD_FILL_SUM = 0, 1, 2
 UPSCALE_METHOD = {"dmm": 0, "eam": 1, "eam_plus": 2}  # PFD_UPSCALE_*
 PFD_COMPARE_OWN, PFD_COMPARE_F64 = 0, 1  # pfd_subbasins_area: where `> area_min` is evaluated
 PFD_SUBAREA_FULL = 1  # pfd_subbasins_area flag: follow every cell (tests)
+# the elementwise calls (csrc/elementwise.hip): outcomes a relation accepts, logic ops, reductions
+PFD_EW_LT, PFD_EW_EQ, PFD_EW_GT, PFD_EW_UNORDERED = 1, 2, 4, 8
+PFD_EW_AND, PFD_EW_OR, PFD_EW_XOR, PFD_EW_NOT = 0, 1, 2, 3
+PFD_EW_COUNT, PFD_EW_MIN, PFD_EW_MAX = 0, 1, 2
 
 _FLOAT_CODE = {np.dtype(np.float32): PFD_F32, np.dtype(np.float64): PFD_F64}
 
@@ -53,6 +58,8 @@ def _signatures():
         "pfd_device_count": (i, [pi]),
         "pfd_malloc": (i, [i, sz, pp]),
         "pfd_free": (i, [i, p]),
+        "pfd_malloc_pooled": (i, [i, sz, pp]),
+        "pfd_free_pooled": (i, [i, p]),
         "pfd_memcpy_h2d": (i, [i, p, p, sz]),
         "pfd_memcpy_d2h": (i, [i, p, p, sz]),
         "pfd_device_synchronize": (i, [i]),
@@ -147,6 +154,11 @@ def _signatures():
         "pfd_verify_hand": (i, [p, p, i, p, p, i, pi64]),
         "pfd_checksum_i32": (i, [i, p, i64, pi64]),
         "pfd_count_nonfinite": (i, [i, i, p, i64, pi64]),
+        "pfd_ew_compare": (i, [i, i, i, p, i, i64, f64, p, i64]),
+        "pfd_ew_logic": (i, [i, i, p, p, p, i64]),
+        "pfd_ew_where": (i, [i, i, p, p, p, i64, f64, p, i64]),
+        "pfd_ew_convert": (i, [i, i, p, i, p, i64]),
+        "pfd_ew_reduce": (i, [i, i, i, p, i64, pi64, pf64, pi]),
         "pfd_synth_d8": (i, synth),
         "pfd_synth_elev_f32": (i, synth),
         "pfd_synth_mosaic": (i, [i, p, i64, i64, i64, i64, p]),
@@ -313,20 +325,44 @@ def alloc_stats() -> dict:
     return {k: int(v) for k, v in zip(keys, a)}
 
 
+# Bytes the Python side itself moves with DeviceBuffer.upload / download (pfd_memcpy_h2d / pfd_memcpy_d2h): those copies
+# are no staging copies of an API call, so pfd_transfer_stats does not see them — DeviceArray's to_device and .numpy() are
+# counted here, and a caller that wants ALL host <-> device traffic of a stretch of code reads both accounts.
+_buffer_traffic = dict(h2d_bytes=0, h2d_copies=0, h2d_ms=0.0, d2h_bytes=0, d2h_copies=0, d2h_ms=0.0)
+
+
+def buffer_transfer_stats(reset: bool = True) -> dict:
+    """Host <-> device traffic of ``DeviceBuffer.upload`` / ``download`` in this process since the last reset: bytes, number
+    of copies and wall milliseconds per direction.  The complement of ``transfer_stats`` (the staging copies inside the
+    library's calls), which never counts these."""
+    out = dict(_buffer_traffic)
+    if reset:
+        for k in _buffer_traffic:
+            _buffer_traffic[k] = 0.0 if k.endswith("_ms") else 0
+    return out
+
+
 class DeviceBuffer:
     """A plain HBM allocation owned by Python (no torch): bench.py keeps the D8 raster and the
     result resident with these and passes them with memspace=PFD_DEVICE."""
 
-    def __init__(self, nbytes: int, device: int = 0):
-        self.device, self.nbytes = device, int(nbytes)
+    def __init__(self, nbytes: int, device: int = 0, pooled: bool = False):
+        """``pooled``: from the library's caching allocator (``pfd_malloc_pooled``: the reserved arena, then cached blocks)
+        instead of a ``hipMalloc`` of its own — for buffers that come and go with every call (``DeviceArray``)."""
+        self.device, self.nbytes, self.pooled = device, int(nbytes), bool(pooled)
         p = C.c_void_p()
-        check(lib().pfd_malloc(device, C.c_size_t(self.nbytes), C.byref(p)))
+        alloc = lib().pfd_malloc_pooled if self.pooled else lib().pfd_malloc
+        check(alloc(device, C.c_size_t(self.nbytes), C.byref(p)))
         self.addr = p.value
 
     def upload(self, arr: np.ndarray):
         arr = np.ascontiguousarray(arr)
         assert arr.nbytes <= self.nbytes
+        t0 = time.perf_counter()
         check(lib().pfd_memcpy_h2d(self.device, C.c_void_p(self.addr), ptr(arr), C.c_size_t(arr.nbytes)))
+        _buffer_traffic["h2d_bytes"] += arr.nbytes
+        _buffer_traffic["h2d_copies"] += 1
+        _buffer_traffic["h2d_ms"] += (time.perf_counter() - t0) * 1e3
         return self
 
     def download(self, dtype, shape, offset_bytes: int = 0, out=None) -> np.ndarray:
@@ -335,12 +371,17 @@ class DeviceBuffer:
             out = np.empty(shape, dtype)
         assert out.dtype == np.dtype(dtype) and out.flags.c_contiguous and out.size == int(np.prod(shape))
         assert out.nbytes + offset_bytes <= self.nbytes
+        t0 = time.perf_counter()
         check(lib().pfd_memcpy_d2h(self.device, ptr(out), C.c_void_p(self.addr + offset_bytes), C.c_size_t(out.nbytes)))
+        _buffer_traffic["d2h_bytes"] += out.nbytes
+        _buffer_traffic["d2h_copies"] += 1
+        _buffer_traffic["d2h_ms"] += (time.perf_counter() - t0) * 1e3
         return out
 
     def free(self):
         if self.addr:
-            check(lib().pfd_free(self.device, C.c_void_p(self.addr)))
+            release = lib().pfd_free_pooled if self.pooled else lib().pfd_free
+            check(release(self.device, C.c_void_p(self.addr)))
             self.addr = None
 
     def __del__(self):
@@ -1161,6 +1202,37 @@ def checksum_i32(buf, n: int, device: int = 0) -> int:
     out = C.c_int64(0)
     check(lib().pfd_checksum_i32(device, ptr(buf), int(n), C.byref(out)))
     return int(out.value)
+
+
+# -- elementwise calls on device buffers (csrc/elementwise.hip; pyflwdir_amd/device_array.py is their front end) --------
+def ew_compare(a, code, rel, compare_code, scalar_i, scalar_f, out, n, device=0):
+    check(lib().pfd_ew_compare(int(device), int(rel), int(code), ptr(a), int(compare_code), int(scalar_i), float(scalar_f),
+                               ptr(out), int(n)))
+    return out
+
+
+def ew_logic(op, a, b, out, n, device=0):
+    check(lib().pfd_ew_logic(int(device), int(op), ptr(a), ptr(b), ptr(out), int(n)))
+    return out
+
+
+def ew_where(mask, code, a, b, scalar_i, scalar_f, out, n, device=0):
+    """``b`` None: the scalar takes its place."""
+    check(lib().pfd_ew_where(int(device), int(code), ptr(mask), ptr(a), ptr(b), int(scalar_i), float(scalar_f), ptr(out),
+                             int(n)))
+    return out
+
+
+def ew_convert(a, src_code, dst_code, out, n, device=0):
+    check(lib().pfd_ew_convert(int(device), int(src_code), ptr(a), int(dst_code), ptr(out), int(n)))
+    return out
+
+
+def ew_reduce(op, a, code, n, device=0):
+    """(int result, float result, a NaN was seen) of pfd_ew_reduce."""
+    ri, rf, nan = C.c_int64(0), C.c_double(0.0), C.c_int(0)
+    check(lib().pfd_ew_reduce(int(device), int(op), int(code), ptr(a), int(n), C.byref(ri), C.byref(rf), C.byref(nan)))
+    return int(ri.value), float(rf.value), bool(nan.value)
 
 
 # -- synthetic rasters generated in HBM ---------------------------------------------------------

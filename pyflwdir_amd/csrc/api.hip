@@ -582,6 +582,23 @@ extern "C" int pfd_free(int device, void *ptr) {
   if (ptr) HIPCHK(hipFree(ptr));
   return PFD_OK;
 }
+// the same pair on the library's own allocator (reserved arena, size-class cache, then hipMalloc): see include/pfd.h
+extern "C" int pfd_malloc_pooled(int device, size_t bytes, void **ptr) {
+  if (!ptr) {
+    pfd_set_error("pfd_malloc_pooled: NULL ptr");
+    return PFD_EINVAL;
+  }
+  *ptr = nullptr;
+  PFDCHK(select_device(device));
+  return pfd_dmalloc(ptr, bytes ? bytes : 16);
+}
+extern "C" int pfd_free_pooled(int device, void *ptr) {
+  PFDCHK(select_device(device));
+  // pfd_dfree waits for the calling thread's last HANDLE stream (or the device), not for the null stream of the pfd_ew_*
+  // calls: enough only because every one of those synchronises before it returns (include/pfd.h, "memory spaces")
+  pfd_dfree(ptr);
+  return PFD_OK;
+}
 extern "C" int pfd_memcpy_h2d(int device, void *dst_dev, const void *src_host, size_t bytes) {
   PFDCHK(select_device(device));
   HIPCHK(hipMemcpy(dst_dev, src_host, bytes, hipMemcpyHostToDevice));

@@ -23,6 +23,10 @@ Mirrors (names, argument meaning, return conventions, error messages):
 * ``add_pits`` / ``order_cells``       reference pyflwdir/flwdir.py:231-279, pyflwdir/pyflwdir.py:299-315
 * ``_check_data`` / ``_check_idxs_xy`` reference pyflwdir/flwdir.py:782-811, pyflwdir/pyflwdir.py:1548-1566
 
+Not in the reference: the sweeps that return one value per cell take ``resident=True`` and then return a
+``DeviceArray`` (pyflwdir_amd/device_array.py) that stays in HBM, and they accept ``DeviceArray`` arguments wherever they
+accept arrays, so that a chain of calls moves nothing per-cell over PCIe ("Resident rasters").
+
 The host keeps the uint8 D8 raster (1 byte/cell); ``idxs_ds`` / ``idxs_seq`` (4-8 bytes/cell)
 are public attributes of the reference and are materialised lazily, on request, by the GPU.
 There is no CPU fallback: without the HIP library or a device the methods raise.
@@ -39,6 +43,7 @@ from . import _hip
 from . import gis
 from . import nextxy as core_nextxy
 from ._affine import get_affine
+from .device_array import DeviceArray, to_device
 
 Affine = get_affine()
 
@@ -612,7 +617,7 @@ class FlwdirRaster(object):
         return gis.idxs_to_coords(idxs, self.transform, self.shape, **kwargs)
 
     # -- the hot path -------------------------------------------------------------------------
-    def upstream_area(self, unit="cell", exact=True):
+    def upstream_area(self, unit="cell", exact=True, resident=False):
         """Upstream area map; reference pyflwdir/pyflwdir.py:770-801.  ``unit="cell"`` returns the
         int32 upstream cell count; other units accumulate the cell-area grid (float64 for
         lat/lon grids, float32 for projected ones).  -9999 on nodata cells.
@@ -624,17 +629,35 @@ class FlwdirRaster(object):
         times faster on a fresh raster because it needs no ordering plan.  It is never offered for float32 sums
         (projected grids): a sequential float32 sum drifts from the real-number sum by more than the 1e-6 this path
         promises, so only the exact order reproduces it.  Whatever the fast form cannot take (cycles, general graphs) is
-        answered by the exact form."""
+        answered by the exact form.
+
+        ``resident`` (not in the reference): return a ``DeviceArray`` that stays in HBM instead of a numpy array."""
         unit = str(unit).lower()
         if unit not in gis.AREA_FACTORS:
             fstr = '", "'.join(gis.AREA_FACTORS.keys())
             raise ValueError(f'Unknown unit: {unit}, select from "{fstr}".')
+        if resident:
+            self._resident_refusals("upstream_area")
         if unit == "cell":
+            if resident:
+                out = self._dev_out(np.int32)
+                self._h.upstream_area_cell(out=out._buf, memspace=_hip.PFD_DEVICE)
+                return out
             return self._h.upstream_area_cell().reshape(self.shape)
         # the cell area of a regular grid depends on the row only: hand the device one value per row
         # (element for element the reference's  area / AREA_FACTORS[unit]) instead of an n-element grid
         rows = np.ascontiguousarray(gis.area_rows(self.transform, self.shape, self.latlon, unit="m2")
                                     / gis.AREA_FACTORS[unit])
+        if resident:  # the same two calls as below, with the result left in HBM
+            out = self._dev_out(rows.dtype)
+            if not exact and rows.dtype == np.float64:
+                got, quantum = self._h.upstream_area_rows_fixed(rows, out=out._buf, memspace=_hip.PFD_DEVICE)
+                if got is not None:
+                    self._last_quantum = quantum
+                    return out
+            self._h.accuflux_rows(rows, _PAYLOAD[rows.dtype], nodata_i=-9999, nodata_f=-9999.0, has_nodata=1,
+                                  direction=_hip.PFD_UP, mask_invalid=1, out=out._buf, memspace=_hip.PFD_DEVICE)
+            return out
         nb = self._row_blocks_needed()
         if not exact and rows.dtype == np.float64 and self._d8 is not None:
             # (one handle whatever the size: the tiled engine addresses tiles and slots, not cells — also beyond 2**32 - 2
@@ -654,10 +677,19 @@ class FlwdirRaster(object):
                                     direction=_hip.PFD_UP, mask_invalid=1)
         return out.reshape(self.shape)
 
-    def accuflux(self, data, nodata=-9999, direction="up"):
-        """Accumulate ``data`` along the flow directions; reference pyflwdir/flwdir.py:567-602."""
+    def accuflux(self, data, nodata=-9999, direction="up", resident=False):
+        """Accumulate ``data`` along the flow directions; reference pyflwdir/flwdir.py:567-602.  ``data`` may be a
+        ``DeviceArray``; ``resident=True`` returns one (32- and 64-bit payloads)."""
         if direction not in ("up", "down"):
             raise ValueError(f'Unknown flow direction: {direction}, select from ["up", "down"].')
+        if resident or isinstance(data, DeviceArray):
+            dev, shape = self._dev_payload(data, "data", "accuflux")
+            _, code, nd_i, nd_f, has_nd = _payload_codes(dev.dtype, nodata)
+            out = self._dev_out(dev.dtype)
+            self._h.accuflux(dev._buf, code, nodata_i=nd_i, nodata_f=nd_f, has_nodata=has_nd,
+                             direction=_hip.PFD_UP if direction == "up" else _hip.PFD_DOWN, out=out._buf,
+                             memspace=_hip.PFD_DEVICE)
+            return self._dev_result(out, resident, shape)
         data = np.asarray(data)
         flat = self._check_data(data, "data")
         if flat.dtype in _NARROW_INT:
@@ -708,18 +740,29 @@ class FlwdirRaster(object):
                                       "wraps around there); pass the data as int32 / int64")
         return out.astype(dt)
 
-    def fillnodata(self, data, nodata, direction="down", how="max"):
+    def fillnodata(self, data, nodata, direction="down", how="max", resident=False):
         """Fill the cells of ``data`` that hold ``nodata`` from the nearest valid cell up- or downstream; reference
         pyflwdir/flwdir.py:360-392 (core.fillnodata_upstream / fillnodata_downstream, core.py:120-188).  ``"up"``: a
         nodata cell takes the value of the first valid cell on its downstream path; ``"down"``: a nodata cell takes the
         values of its valid (or filled) upstream cells, merged at confluences with ``how`` ("max", "min" or "sum", in the
         serial loop's order, sums wrapping in the payload dtype).  Cells off the reference's ``idxs_seq`` are left as they
-        are.  One handle, the general engine, or row blocks beyond 2**32 - 2 cells."""
+        are.  One handle, the general engine, or row blocks beyond 2**32 - 2 cells.  ``data`` may be a ``DeviceArray``;
+        ``resident=True`` returns one (32- and 64-bit payloads)."""
         direction = str(direction).lower()
         if direction not in ("up", "down"):
             raise ValueError(f'Unknown flow direction: {direction}, select from ["up", "down"].')
         if direction == "down" and how not in ["min", "max", "sum"]:  # (the reference's assert, as the same exception type)
             raise AssertionError(f'Unknown method: {how}, select from ["min", "max", "sum"].')
+        if resident or isinstance(data, DeviceArray):
+            dev, shape = self._dev_payload(data, "data", "fillnodata")
+            code, nd_i, nd_f, has_nd = _fill_codes(dev.dtype, nodata)
+            hw = {"max": _hip.PFD_FILL_MAX, "min": _hip.PFD_FILL_MIN, "sum": _hip.PFD_FILL_SUM}[how] if direction == "down" \
+                else _hip.PFD_FILL_MAX
+            out = self._dev_out(dev.dtype)
+            self._h.fillnodata(dev._buf, code, nodata_i=nd_i, nodata_f=nd_f, has_nodata=has_nd,
+                               direction=_hip.PFD_UP if direction == "up" else _hip.PFD_DOWN, how=hw, out=out._buf,
+                               memspace=_hip.PFD_DEVICE)
+            return self._dev_result(out, resident, shape)
         data = np.asarray(data)
         flat = self._check_data(data, "data")
         lanes, code, nd_i, nd_f, has_nd = _fill_args(flat, nodata)
@@ -739,11 +782,19 @@ class FlwdirRaster(object):
             out = out.astype(flat.dtype)
         return out.reshape(data.shape)
 
-    def upstream_sum(self, data, mv=-9999):
+    def upstream_sum(self, data, mv=-9999, resident=False):
         """Sum of the values of the cells directly upstream; reference pyflwdir/flwdir.py:412-433,
-        pyflwdir/arithmetics.py:147-169 (incl. where its serial loop writes the missing value)."""
+        pyflwdir/arithmetics.py:147-169 (incl. where its serial loop writes the missing value).  ``data`` may be a
+        ``DeviceArray``; ``resident=True`` returns one."""
         if self._d8 is None:  # (general graphs: the C layer would refuse as well)
             raise NotImplementedError("upstream_sum is not available for flow directions with non-neighbour links")
+        if resident or isinstance(data, DeviceArray):
+            dev, shape = self._dev_payload(data, "data", "upstream_sum")
+            _, code, nd_i, nd_f, has_nd = _payload_codes(dev.dtype, mv)
+            out = self._dev_out(dev.dtype)
+            self._h.upstream_sum(dev._buf, code, nodata_i=nd_i, nodata_f=nd_f, has_nodata=has_nd, out=out._buf,
+                                 memspace=_hip.PFD_DEVICE)
+            return self._dev_result(out, resident, shape)
         data = np.asarray(data)
         flat = self._check_data(data, "data")
         view, code, nd_i, nd_f, has_nd = _payload_args(flat, mv)
@@ -755,9 +806,23 @@ class FlwdirRaster(object):
         out = self._h.upstream_sum(view, code, nodata_i=nd_i, nodata_f=nd_f, has_nodata=has_nd)
         return out.view(flat.dtype).reshape(data.shape)
 
-    def stream_order(self, type="strahler", mask=None):
+    def stream_order(self, type="strahler", mask=None, resident=False):
         """Strahler stream order map (uint8); reference pyflwdir/flwdir.py:508-547.  Like the
-        reference, the result is cached under "strord" when ``cache=True`` regardless of mask."""
+        reference, the result is cached under "strord" when ``cache=True`` regardless of mask.
+
+        ``mask`` may be a ``DeviceArray`` and ``resident=True`` returns one (``type="strahler"``); such a call computes
+        what it is asked and neither reads nor writes the "strord" cache, which stays the numpy cache of the reference."""
+        if resident or isinstance(mask, DeviceArray):
+            if type.lower() != "strahler":
+                if type.lower() != "classic":
+                    raise ValueError(f'Unknown stream order type: {type}, select from ["strahler", "classic"].')
+                raise NotImplementedError('stream_order(type="classic") has no device-resident form: it follows the main '
+                                          "upstream cells, a host array; call it with numpy arrays (mask.numpy())")
+            self._resident_refusals("stream_order")
+            m = self._dev_mask(mask)
+            out = self._dev_out(np.uint8)
+            self._h.strahler(None if m is None else m._buf, out=out._buf, memspace=_hip.PFD_DEVICE)
+            return self._dev_result(out, resident)
         mask = self._check_data(mask, "mask", optional=True)
         if type.lower() == "strahler":
             if "strord" in self._cached:
@@ -789,12 +854,20 @@ class FlwdirRaster(object):
             raise ValueError(f'Unknown stream order type: {type}, select from ["strahler", "classic"].')
         return strord.reshape(self.shape)
 
-    def stream_distance(self, mask=None, unit="cell"):
+    def stream_distance(self, mask=None, unit="cell", resident=False):
         """Distance to the outlet or to the next downstream True cell of ``mask``: int32 cell counts
-        (``unit="cell"``) or float32 metres (``unit="m"``); reference pyflwdir/pyflwdir.py:837-863."""
+        (``unit="cell"``) or float32 metres (``unit="m"``); reference pyflwdir/pyflwdir.py:837-863.  ``mask`` may be a
+        ``DeviceArray``; ``resident=True`` returns one."""
         unit = str(unit).lower()
         if unit not in ["m", "cell"]:
             raise ValueError(f'Unknown unit: {unit}, select from "m", "cell"')
+        if resident or isinstance(mask, DeviceArray):
+            self._resident_refusals("stream_distance")
+            m = self._dev_mask(mask)
+            tab = None if unit == "cell" else gis.step_length_table(self.shape[0], self.latlon, self.transform)
+            out = self._dev_out(np.int32 if tab is None else np.float32)
+            self._h.stream_distance(None if m is None else m._buf, tab, out=out._buf, memspace=_hip.PFD_DEVICE)
+            return self._dev_result(out, resident)
         mask = self._check_data(mask, "mask", optional=True)
         m = None if mask is None else np.ascontiguousarray(mask != 0).view(np.uint8)
         if unit == "cell":
@@ -840,8 +913,9 @@ class FlwdirRaster(object):
             return self._cached["idxs_us_main"]
         return self.main_upstream()
 
-    def basins(self, idxs=None, xy=None, ids=None, **kwargs):
-        """(Sub)basin map with a unique ID per (sub)basin; reference pyflwdir/pyflwdir.py:564-599."""
+    def basins(self, idxs=None, xy=None, ids=None, resident=False, **kwargs):
+        """(Sub)basin map with a unique ID per (sub)basin; reference pyflwdir/pyflwdir.py:564-599.  ``resident=True``
+        returns a ``DeviceArray`` (ids of a dtype it holds: uint8, int8, int32, uint32, int64)."""
         if idxs is None and xy is None:
             idxs = self.idxs_pit
         else:
@@ -860,6 +934,11 @@ class FlwdirRaster(object):
         idxs64 = idxs.astype(np.int64)
         if np.any(idxs64 < 0) or np.any(idxs64 >= self.size):
             raise IndexError("idxs outside domain")
+        if resident:
+            self._resident_refusals("basins")
+            out = self._dev_out(ids.dtype)
+            self._h.basins(idxs64, ids, out=out._buf, memspace=_hip.PFD_DEVICE)
+            return out
         nb = self._row_blocks_needed()
         if nb > 1:
             # beyond 32-bit cell indices: the tiled label query addresses tiles and slots and runs on the whole raster
@@ -1228,8 +1307,12 @@ class FlwdirRaster(object):
             raise NotImplementedError("stream_order: the raster is too large for the cycle check that the row-block "
                                       "Strahler order needs (more than 65535 tile rows or ~4e9 perimeter slots)")
 
-    def hand(self, drain, elevtn):
-        """Height above the nearest drain (float64); reference pyflwdir/pyflwdir.py:1485-1511."""
+    def hand(self, drain, elevtn, resident=False):
+        """Height above the nearest drain (float64); reference pyflwdir/pyflwdir.py:1485-1511.  ``drain`` and ``elevtn``
+        may be ``DeviceArray`` s (``drain == 1`` and the widening of an integer elevation then run on the device; an
+        int64 elevation, whose conversion to float64 rounds, is taken from the host only); ``resident=True`` returns one."""
+        if resident or isinstance(drain, DeviceArray) or isinstance(elevtn, DeviceArray):
+            return self._hand_resident(drain, elevtn, resident)
         drain = self._check_data(drain, "drain")
         elevtn = self._check_data(elevtn, "elevtn")
         drain_u8 = np.ascontiguousarray(drain == 1).view(np.uint8)
@@ -1245,6 +1328,34 @@ class FlwdirRaster(object):
 
             return dist.hand_blocks(self._d8, nb, drain_u8, np.ascontiguousarray(elevtn))[0].reshape(self.shape)
         return self._h.hand(drain_u8, np.ascontiguousarray(elevtn), code).reshape(self.shape)
+
+    def _hand_resident(self, drain, elevtn, resident):
+        """``hand`` with its per-cell arguments and its result in HBM: the host expressions of ``hand`` through the
+        kernels of csrc/elementwise.hip for device arguments, through numpy (then one upload) for host arguments."""
+        self._resident_refusals("hand")
+        if isinstance(drain, DeviceArray):
+            d = self._dev_arg(drain, "drain")
+            d = d if d.dtype == np.bool_ else d == 1  # (True == 1: a bool array is its own answer)
+        else:
+            d = self._to_dev(self._check_data(drain, "drain") == 1)
+        if isinstance(elevtn, DeviceArray):
+            e = self._dev_arg(elevtn, "elevtn")
+            if e.dtype == np.int64:
+                raise NotImplementedError("hand: an int64 elevation is rounded to float64, which the device conversions "
+                                          "(exact ones only) do not offer; pass it as a numpy array or as float64")
+            if e.dtype.kind != "f":
+                e = (e.astype(np.int32) if e.dtype.itemsize == 1 else e).astype(np.float64)
+        else:
+            e = self._check_data(elevtn, "elevtn")
+            if e.dtype == np.float64 or e.dtype.kind in "iub":
+                e = e.astype(np.float64, copy=False)
+            elif e.dtype != np.float32:
+                raise NotImplementedError(f"elevation dtype {e.dtype} is not supported on the HIP path")
+            e = self._to_dev(e)
+        out = self._dev_out(np.float64)
+        self._h.hand(d._buf, e._buf, _hip.PFD_F32 if e.dtype == np.float32 else _hip.PFD_F64, out=out._buf,
+                     memspace=_hip.PFD_DEVICE)
+        return self._dev_result(out, resident)
 
     def ucat_area(self, idxs_out, unit="cell"):
         """Unit catchment map (high resolution) and area (low resolution); reference
@@ -1460,11 +1571,17 @@ class FlwdirRaster(object):
         return rivmed.reshape(idxs_out.shape)
 
     # -- windows along the flow path (csrc/window.hip: one lane per cell and a bounded walk) ----------------
-    def downstream(self, data):
+    def downstream(self, data, resident=False):
         """The value of the next downstream cell: ``out = data.copy(); out[mask] = data[idxs_ds[mask]]`` — a pit takes
         its own value, a nodata flow cell keeps its own; reference pyflwdir/flwdir.py:394-410.  A gather of 1-, 2-, 4- or
-        8-byte elements: every numpy dtype of those sizes, ``bool`` included; dtype and shape of ``data``."""
+        8-byte elements: every numpy dtype of those sizes, ``bool`` included; dtype and shape of ``data``.  ``data`` may be
+        a ``DeviceArray``; ``resident=True`` returns one (of a dtype a ``DeviceArray`` holds)."""
         self._subgrid_refusals("downstream", walks=False)
+        if resident or isinstance(data, DeviceArray):
+            dev, shape = self._dev_payload(data, "data", "downstream", narrow_ok=True)
+            out = self._dev_out(dev.dtype)
+            self._h.downstream(dev._buf, elem_bytes=dev.dtype.itemsize, out=out._buf, memspace=_hip.PFD_DEVICE)
+            return self._dev_result(out, resident, shape)
         flat = self._check_data(data, "data")
         if flat.dtype.kind not in "biufcmM" or flat.dtype.itemsize not in (1, 2, 4, 8):
             raise NotImplementedError(f"downstream: data dtype {flat.dtype} is not supported on the HIP path "
@@ -1693,6 +1810,65 @@ class FlwdirRaster(object):
             return out.reshape(self.shape)
         return self._h.floodplains(np.ascontiguousarray(elevtn), code, is_stream, hs).reshape(self.shape)
 
+    # -- device-resident arguments and results (pyflwdir_amd/device_array.py; DESIGN.md "Resident rasters") ----------
+    def _resident_refusals(self, what):
+        """What the device-resident form of a sweep does not take: one handle and one ``memspace`` per C call."""
+        if self._d8 is None:
+            raise NotImplementedError(f"{what}: device-resident arrays are not offered on a general idxs_ds graph; call it "
+                                      "with numpy arrays and without resident=True")
+        if self._row_blocks_needed() > 1:
+            raise NotImplementedError(f"{what}: a raster beyond 2**32 - 2 cells runs in row blocks, which assemble their "
+                                      "result on the host; call it with numpy arrays and without resident=True")
+
+    def _dev_arg(self, data, name):
+        """A ``DeviceArray`` given for the per-cell argument ``name``: of the raster's size, alive, on the handle's GPU."""
+        data._live()
+        if data.size != self.size:
+            raise ValueError(f'"{name}" size does not match.')
+        if data.device != self.device:
+            raise ValueError(f'"{name}" lives on GPU {data.device}, the raster on GPU {self.device}')
+        return data
+
+    def _to_dev(self, flat):
+        return to_device(flat, self.device)
+
+    def _dev_out(self, dtype):
+        return DeviceArray.empty(self.shape, dtype, self.device)
+
+    def _dev_result(self, out, resident, shape=None):
+        """The result of a device call as the caller asked for it: the DeviceArray, or its download."""
+        if shape is not None and tuple(shape) != out.shape:
+            out = out.reshape(shape)
+        return out if resident else out.numpy()
+
+    def _dev_mask(self, mask, name="mask"):
+        """``mask != 0`` as a bool DeviceArray (None stays None): a kernel for a device mask, numpy and one upload of a
+        byte per cell for a host mask."""
+        if mask is None:
+            return None
+        if isinstance(mask, DeviceArray):
+            m = self._dev_arg(mask, name)
+            return m if m.dtype == np.bool_ else m != 0
+        return self._to_dev(self._check_data(mask, name) != 0)
+
+    def _dev_payload(self, data, name, what, narrow_ok=False):
+        """(DeviceArray, shape of the result) of a per-cell payload that is a DeviceArray or is uploaded as it is.  The
+        narrow integers of accuflux / fillnodata are widened and range-checked with numpy on the host path only."""
+        self._resident_refusals(what)
+        if isinstance(data, DeviceArray):
+            dev, shape = self._dev_arg(data, name), data.shape
+        else:
+            data = np.asarray(data)
+            flat = self._check_data(data, name)
+            shape = data.shape if data.size == self.size else self.shape
+            dev = None
+        dt = (dev if dev is not None else flat).dtype
+        if not narrow_ok and (dt.itemsize < 4 or dt.kind not in "iuf"):
+            raise NotImplementedError(f"{what}: a {dt} payload has no device-resident form (the host path widens and "
+                                      "range-checks it with numpy); call it with a numpy array and without resident=True, "
+                                      "or pass the data as int32 / int64 / float32 / float64")
+        return (dev if dev is not None else self._to_dev(flat)), shape
+
     # -- shortcuts ------------------------------------------------------------------------------
     def _check_data(self, data, name, optional=False, flatten=True, **kwargs):
         """Check data shape and size, return the flattened array; reference
@@ -1782,21 +1958,27 @@ def _effective_area_mask(cellsize, shape, r_ratio=0.5):
 
 
 def _payload_args(flat, nodata):
-    """Map a flattened payload + Python nodata to the device dtype code and nodata arguments.
+    """Map a flattened payload + Python nodata to the device dtype code and nodata arguments (``_payload_codes``); the
+    payload comes back as the contiguous array the kernels read (unsigned integers viewed as signed)."""
+    vdt, code, nd_i, nd_f, has_nd = _payload_codes(flat.dtype, nodata)
+    return np.ascontiguousarray(flat if vdt == flat.dtype else flat.view(vdt)), code, nd_i, nd_f, has_nd
+
+
+def _payload_codes(dt, nodata):
+    """(dtype the kernels read the payload as, its code, nodata_i, nodata_f, has_nodata) for a payload of dtype ``dt``.
     `has_nodata` is False when the reference's comparison ``accu != nodata`` can never be False
     (NaN, out-of-range or non-integral nodata for integer data, negative nodata for unsigned)."""
-    dt = flat.dtype
+    dt = np.dtype(dt)
     if dt == np.uint32:
-        view, info = flat.view(np.int32), np.iinfo(np.uint32)
+        view, info = np.dtype(np.int32), np.iinfo(np.uint32)
     elif dt == np.uint64:
-        view, info = flat.view(np.int64), np.iinfo(np.uint64)
+        view, info = np.dtype(np.int64), np.iinfo(np.uint64)
     elif dt in _PAYLOAD:
-        view, info = flat, (np.iinfo(dt) if dt.kind == "i" else None)
+        view, info = dt, (np.iinfo(dt) if dt.kind == "i" else None)
     else:
         raise NotImplementedError(f"payload dtype {dt} is not supported on the HIP path "
                                   "(supported: int8 ... int64, uint8 ... uint64, float32, float64)")
-    view = np.ascontiguousarray(view)
-    code = _PAYLOAD[view.dtype]
+    code = _PAYLOAD[view]
     if dt.kind == "f":
         nd = float(nodata)
         if nd != nd:
@@ -1811,7 +1993,7 @@ def _payload_args(flat, nodata):
         return view, code, 0, 0.0, 0
     nd = int(nodata)
     if dt.kind == "u":  # reinterpret as the signed kernel type
-        nd = int(np.array([nd], dtype=dt).view(view.dtype)[0])
+        nd = int(np.array([nd], dtype=dt).view(view)[0])
     return view, code, nd, 0.0, 1
 
 
@@ -1831,24 +2013,31 @@ def _fill_args(flat, nodata):
     that max / min compare unsigned.  ``has_nodata`` is 0 when no element can compare equal to ``nodata`` (as in
     _payload_args): the result is then a copy of the payload."""
     dt = flat.dtype
+    code, nd_i, nd_f, has_nd = _fill_codes(dt, nodata)
+    lanes = np.ascontiguousarray(flat.astype(np.int32) if dt.itemsize < 4 else flat)
+    return lanes, code, nd_i, nd_f, has_nd
+
+
+def _fill_codes(dt, nodata):
+    """(dtype code, nodata_i, nodata_f, has_nodata) of ``_fill_args`` for a payload of dtype ``dt``."""
+    dt = np.dtype(dt)
     if dt not in _FILL_CODES:
         raise NotImplementedError(f"fillnodata: payload dtype {dt} is not supported on the HIP path "
                                   "(supported: int8 ... int64, uint8 ... uint64, float32, float64)")
     code = _FILL_CODES[dt]
-    lanes = np.ascontiguousarray(flat.astype(np.int32) if dt.itemsize < 4 else flat)
     if dt.kind == "f":
         nd = float(nodata)
         if nd != nd:
-            return lanes, code, 0, 0.0, 0
-        return lanes, code, 0, float(dt.type(nd)), 1
+            return code, 0, 0.0, 0
+        return code, 0, float(dt.type(nd)), 1
     info = np.iinfo(dt)
     try:
         integral = float(nodata) == int(nodata)
     except (OverflowError, ValueError, TypeError):
         integral = False
     if not integral or not (info.min <= int(nodata) <= info.max):
-        return lanes, code, 0, 0.0, 0
+        return code, 0, 0.0, 0
     nd = int(nodata)
     if nd > np.iinfo(np.int64).max:  # (uint64: the bits of the value)
         nd -= 1 << 64
-    return lanes, code, nd, 0.0, 1
+    return code, nd, 0.0, 1
